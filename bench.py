@@ -6,16 +6,25 @@ embeddings and decoder, keyframe pose optimisers) — on synthetic Replica
 room0-shaped input (BASELINE.json configs[1]: 4096 rays/iter = 4 keyframes x
 1024 rays, 1x MI355X; ~64 samples/ray).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--extras] [--no-traffic]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py --full [--extras] [--no-traffic] [--no-cpu-baseline] ...
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
 One process per GPU; every rank renders its own keyframes' 4096 rays against
 the replicated octree (weak scaling); the loss is the union batch's and the
 embedding + decoder gradients are summed over ranks.  Rank 0
 prints one JSON line.  Inputs (octree, embeddings, decoder, full-resolution
-keyframes) are resident in HBM before timing starts.  The roofline carries
-kernel durations measured in the headline iterations and HBM bytes from two
-PMC passes over the same iterations (rocprofv3 children, before the JSON).
+keyframes) are resident in HBM before timing starts.
+
+A plain run does what the headline figure needs and no more: set-up, the
+untimed training of the map, W warm-up and K timed iterations, the outputs
+(--dump-outputs: one iteration of the timed path from the seeded initial map,
+comparable between runs and builds), the result line.  --full adds
+everything else the benchmark measures, each in runs of its own: the
+random-init map's timed figure, the
+rooflines (kernel durations measured in marked headline iterations, HBM bytes
+from two PMC passes over the same iterations: rocprofv3 children, before the
+JSON), the other paths (--extras) and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -81,9 +90,22 @@ def parse():
                          "timed, so that it runs on a map in the state Mapping renders (trained: the sparse "
                          "decoder's class mix settles); stops early once the composited fraction is stable. "
                          "0: time the random-init map (the untrained figure is reported beside the trained one)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure, each in runs of its own: the random-init map's "
+                         "timed figure, the rooflines (marked iterations, PMC passes: see --no-traffic), the CPU "
+                         "baseline (see --no-cpu-baseline) and, with --extras, the other paths.  Off: the set-up, "
+                         "the warm-up and the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what one step of the timed path leaves with its caller — the "
+                         "embedding table, the decoder's parameters and the keyframe poses — as DIR/<name>.npy "
+                         "(float32), from a step of its own that starts at the seeded initial map (the same from "
+                         "run to run: see replay_for_dump)")
     ap.add_argument("--probe", action="store_true", help=argparse.SUPPRESS)  # PMC child: headline iterations only
     ap.add_argument("--step-size", type=float, default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    a.full = a.full or a.extras  # the other paths are reported beside the full run's figures
     big = a.scene in ("scannet0000", "multiroom")  # configs/scannet/scannet.yaml:17, configs/arkit/arkit.yaml:17
     if a.width is None:
         a.width = 256 if big else 128
@@ -370,6 +392,28 @@ def measure_traffic(args, step_size):
                 "(headline iterations), median bytes per launch, fetch = 2 x FETCH_SIZE (gfx950)"
 
 
+def dump_outputs(out_dir, emb, dec, kfs):
+    """--dump-outputs: what bundle_adjust_frames leaves with its caller (it
+    returns nothing: it optimises in place) after a step, as float32
+    DIR/<name>.npy — the embedding table, each decoder parameter and the
+    keyframes' poses [frames, 6] (translation, rotation vector).  Config B:
+    ≈ 1.5 MB; the largest scene's table (multiroom: millions of rows) is cut to
+    a seeded sample of rows so that a dump stays below 64 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"embeddings": emb.detach()}
+    for name, p in dec.named_parameters():
+        arrays["decoder." + name] = p.detach()
+    arrays["poses"] = torch.stack([kf.pose.data.detach().reshape(6) for kf in kfs])
+    max_rows = (48 << 20) // (emb.shape[1] * 4)
+    if emb.shape[0] > max_rows:
+        rows = torch.randperm(emb.shape[0], generator=torch.Generator().manual_seed(0))[:max_rows].sort().values
+        arrays["embeddings"] = emb.detach()[rows.to(emb.device)]
+        arrays["embeddings_rows"] = rows.to(torch.float64)  # the sampled rows' indices
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -406,6 +450,10 @@ def main():
     points_encoder = PointsResNet(16).to(device)
     points_encoder.train()
     resnet_optim = torch.optim.Adam(points_encoder.parameters(), lr=5e-3)
+    # --dump-outputs: the seeded initial map and poses (replay_for_dump)
+    seeded = None
+    if args.dump_outputs:
+        seeded = [t.detach().clone() for t in [emb] + list(dec.parameters()) + [kf.pose.data for kf in kfs]]
     stats = {"n": 0, "m": 0, "r_hit": 0, "visits": 0, "s_max": 0}  # the marked (breakdown) runs
     head_stats = dict(stats)  # the headline bundle_adjust_frames iterations
 
@@ -540,6 +588,43 @@ def main():
         torch.cuda.synchronize()
         return trace
 
+    def replay_for_dump():
+        """The arrays --dump-outputs writes.  The map the headline is timed on
+        went through hundreds of training iterations, and the embedding
+        gradient's float atomics add in a different order every run: measured
+        at config B, two runs of one build end ≈ 345 iterations with decoder
+        weights that differ by as much as their own size (max |Δ| 1.3 at max |w|
+        1.1), so that state says nothing about a build.  Nor does a replay of
+        all the timed steps from the seeded map: Adam divides each gradient by
+        its own running size, so rounding noise grows ≈ 1.4 x per iteration
+        (20 iterations: mean |Δ| 1e-4, single decoder weights 1e-2).  What is
+        written instead is ONE step of the timed path, after the measurements:
+        the map, the poses and every optimiser state back at their seeded
+        initial values, the host generator (pixel draws, sampler seeds)
+        re-seeded, then the same bundle_adjust_frames call with one iteration.
+        Its inputs are bit-identical from run to run, the decoder's update is
+        computed in a fixed order, and the embeddings' first Adam step is
+        ± lr wherever the gradient is above rounding: three runs of one build
+        wrote bit-equal decoder parameters and poses and embedding tables
+        within 2e-7 of each other (mean |Δ| 2e-11; measured once,
+        profiles/r07_dump_repeat.txt).  The limit: the dump sees the random-init
+        map's first, un-pipelined iteration only — not the look-ahead query of
+        the later iterations, nor the trained map's class mix."""
+        with torch.no_grad():
+            for p, p0 in zip([emb] + list(dec.parameters()) + [kf.pose.data for kf in kfs], seeded):
+                p.copy_(p0)
+            for opt in [embed_optim, model_optim] + [kf.optim for kf in kfs]:
+                for st in opt.state.values():
+                    for v in st.values():
+                        if torch.is_tensor(v):
+                            v.zero_()  # moments and step count
+        torch.manual_seed(0)
+        ba_calls[0] = 0
+        run_ba(1)
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, emb, dec, kfs)
+
     if args.probe:  # PMC child (measure_traffic): the headline iterations only (after the same training)
         if args.train_iters > 0:
             run_ba(args.train_iters)
@@ -553,16 +638,25 @@ def main():
     untrained, train_trace = None, []
     args.train_iters_done = 0
     if args.train_iters > 0:
-        el_u = timed_ba(args.steps, max(1, args.warmup), record=True)
-        hs_u = dict(head_stats)
-        steps_u = sel_stats.get("steps", 0)
-        m_u = hs_u["m"] / max(hs_u["n"], 1)
-        untrained = {"value": args.frames * args.rays_per_frame * args.steps * world / el_u,
-                     "ms_per_step": 1000.0 * el_u / args.steps, "gpu_ms_per_step": pace.get("gpu_ms_per_step"),
-                     "decoder_kept_fraction": sel_stats["kept_sum"] / steps_u / m_u if steps_u and m_u else None,
-                     "composited_fraction": sel_stats["composited_sum"] / steps_u / m_u if steps_u and m_u else None,
-                     "samples_per_step": m_u}
-        log(f"untrained map: {untrained['ms_per_step']:.4f} ms/step; training (untimed, <= {args.train_iters} it)")
+        if args.full:
+            el_u = timed_ba(args.steps, max(1, args.warmup), record=True)
+            hs_u = dict(head_stats)
+            steps_u = sel_stats.get("steps", 0)
+            m_u = hs_u["m"] / max(hs_u["n"], 1)
+            untrained = {"value": args.frames * args.rays_per_frame * args.steps * world / el_u,
+                         "ms_per_step": 1000.0 * el_u / args.steps, "gpu_ms_per_step": pace.get("gpu_ms_per_step"),
+                         "decoder_kept_fraction": sel_stats["kept_sum"] / steps_u / m_u if steps_u and m_u else None,
+                         "composited_fraction": sel_stats["composited_sum"] / steps_u / m_u
+                         if steps_u and m_u else None,
+                         "samples_per_step": m_u}
+            log(f"untrained map: {untrained['ms_per_step']:.4f} ms/step; training (untimed, <= "
+                f"{args.train_iters} it)")
+        else:
+            # the same calls, neither timed nor recorded: the map's first iterations
+            # of training, so that the headline runs on the map it runs on with --full
+            run_ba(max(1, args.warmup))
+            run_ba(args.steps)
+            log(f"training (untimed, <= {args.train_iters} it)")
         train_trace = train_map(args.train_iters)
         args.train_iters_done = train_trace[-1][0] if train_trace else 0
         log(f"trained {args.train_iters_done} iterations: composited / kept fraction {train_trace[-1][1:]}")
@@ -575,6 +669,75 @@ def main():
                  "optimisers; per-iteration gumbel pixel sampling on the device, keyframe poses optimised) — "
                  "dispatched by bundle_adjust_frames to psvo_map_step_frames")
     eng = head_engine()
+    rays_step = args.frames * args.rays_per_frame
+    value = rays_step * args.steps * world / elapsed
+    ms_per_step = 1000.0 * elapsed / args.steps
+    # the timed steps' statistics (the query's read-backs and the selection's counters)
+    hs = head_stats
+    h_n = max(hs["n"], 1)
+    h_m, h_r, h_v = hs["m"] / h_n, hs["r_hit"] / h_n, hs["visits"] / h_n
+    if world > 1:  # per-GPU averages over the union of the ranks' batches
+        t = torch.tensor([h_m, h_r, h_v], dtype=torch.float64, device=device)
+        dist.all_reduce(t)
+        h_m, h_r, h_v = (float(x) / world for x in t.cpu())
+    steps_sel = sel_stats.get("steps", 0)
+    kept = sel_stats["kept_sum"] / steps_sel if steps_sel else None  # per step (this rank)
+    comp = sel_stats["composited_sum"] / steps_sel if steps_sel else None
+    if world > 1 and kept is not None:
+        t = torch.tensor([kept, comp], dtype=torch.float64, device=device)
+        dist.all_reduce(t)
+        kept, comp = (float(x) / world for x in t.cpu())
+    result = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "rays/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        # the steady-state iteration period as the GPU ran it (events at each step's entry on its
+        # stream) and how often the host had to wait for a query's statistics — a host that never
+        # waits set the pace; one that waits on nearly every step was paced by the GPU
+        "gpu_ms_per_step": pace.get("gpu_ms_per_step"),
+        "pace": dict(pace, note="gpu_ms_per_step excludes each bundle_adjust_frames call's setup / write-back "
+                                "and its first, un-pipelined iteration; ms_per_step is the wall clock of the call"),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": ("synthetic (room0-shaped octree + Replica pinhole RGB-D keyframes, analytic GT); embeddings / "
+                 "decoder / poses trained from random init by %d untimed bundle_adjust_frames iterations on the "
+                 "same keyframes before timing (map_state: %s)" % (args.train_iters_done, "trained"
+                                                                   if args.train_iters_done else "random-init")),
+        "config": {"workload": f"{args.scene}: {args.frames} keyframes x {args.rays_per_frame} rays/iter per GPU, "
+                               f"{tree.count_nodes()} octree nodes, decoder W={args.width}, "
+                               f"{h_m / max(h_r, 1):.1f} samples/hit ray (step {step_size:.5f} m)",
+                   "rays_per_step_per_gpu": rays_step, "samples_per_step": h_m, "hit_rays_per_step": h_r,
+                   "aabb_tests_per_step": h_v,
+                   # the sparse decoder: samples whose gradients can be non-zero (the full decoder runs on
+                   # these) and the composited ones (a compositing weight: z < z_min + truncation)
+                   "decoder_kept_fraction": kept / h_m if kept is not None and h_m else None,
+                   "composited_fraction": comp / h_m if comp is not None and h_m else None,
+                   "map_state": "trained" if args.train_iters_done else "random-init",
+                   "train_iterations": args.train_iters_done,
+                   # (iterations so far, composited fraction, kept fraction) after each training chunk
+                   "train_trace": train_trace,
+                   # the random-init map's timed figure (--full)
+                   "untrained": untrained,
+                   "parallelism": f"dp{world} (ray-sharded, union-batch loss, "
+                                  f"{dist.get_backend() if world > 1 else 'no'} collectives)"},
+        "path": path_desc,
+    }
+    if not args.full:
+        log("done timing")
+        if args.dump_outputs:
+            replay_for_dump()
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    # ---- --full: the figures that take runs of their own
     # the kernels' durations as the headline runs them: HIP events on the
     # launching streams inside the same bundle_adjust_frames iterations
     n_mark = max(5, min(args.steps, 20))
@@ -595,7 +758,6 @@ def main():
         D.TIMER = None
     kt_serial = None
     others = []
-    rays_step = args.frames * args.rays_per_frame
     if args.extras and world == 1:
         # the serialised one-stream breakdown and the other paths, on a separate
         # engine over pre-built world-space batches (fixed poses)
@@ -661,10 +823,6 @@ def main():
         others.append({"path": "drop-in autograd (render_rays + Criterion + backward + psvo.optim.Adam)",
                        "value": rays_step * other_steps / el2, "ms_per_step": 1000.0 * el2 / other_steps})
         engine.close()
-    rays_per_step = rays_step
-    total_rays = rays_per_step * args.steps * world
-    value = total_rays / elapsed
-    ms_per_step = 1000.0 * elapsed / args.steps
 
     # Rooflines.  Primary — the north star's "octree query+interp
     # kernel", as the kernels launched for it: algorithmic bytes per step =
@@ -679,13 +837,6 @@ def main():
     # one-stream serialised durations are reported with --extras.  Traffic:
     # PMC-counted HBM bytes of the same iterations (measure_traffic).
     # Secondary — the decoder (dominant by time), MFMA-bound.
-    hs = head_stats
-    h_n = max(hs["n"], 1)
-    h_m, h_r, h_v = hs["m"] / h_n, hs["r_hit"] / h_n, hs["visits"] / h_n
-    if world > 1:  # per-GPU averages over the union of the ranks' batches
-        t = torch.tensor([h_m, h_r, h_v], dtype=torch.float64, device=device)
-        dist.all_reduce(t)
-        h_m, h_r, h_v = (float(x) / world for x in t.cpu())
     fused_ib = args.width == 128  # interp bwd inside k_mlp_bwd3
     q_keys = ("intersect", "sample", "points", "interp_fwd") + (() if fused_ib else ("interp_bwd",))
     # a region the step did not mark (the headline has no separate compaction) counts 0
@@ -762,13 +913,6 @@ def main():
     macs = 16 * w + w * w + w * 129 + 144 * w + w * 3  # nrgbd.py:80-146, depth 2, sdf_dim 128, in_dim 16
     trunk = 16 * w + w * w + w  # h1, h2 and the sdf row: what the sparse decoder runs on every sample
     flops_mlp = 3 * 2.0 * macs * h_m  # algorithmic: the reference's forward + δ chain + weight gradients, every sample
-    steps_sel = sel_stats.get("steps", 0)
-    kept = sel_stats["kept_sum"] / steps_sel if steps_sel else None  # per step (this rank)
-    comp = sel_stats["composited_sum"] / steps_sel if steps_sel else None
-    if world > 1 and kept is not None:
-        t = torch.tensor([kept, comp], dtype=torch.float64, device=device)
-        dist.all_reduce(t)
-        kept, comp = (float(x) / world for x in t.cpu())
     # executed: the sdf trunk on every sample; the whole decoder forward and backward on the kept
     # ones — width 128 on the composited ones only, the trunk forward + backward (δ chain, dW1, dW2,
     # the sdf row of W3) on the kept samples that only the direct sdf loss reaches (class B); width
@@ -799,44 +943,7 @@ def main():
     else:
         roof_ib = bw_roof("k_interp_bwd", 1664.0 * m_bwd, kt_overlap["interp_bwd"],
                           tr.get("bwd_fused_bytes_per_launch"), kt_serial["interp_bwd"] if kt_serial else None)
-    result = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "rays/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        # the steady-state iteration period as the GPU ran it (events at each step's entry on its
-        # stream) and how often the host had to wait for a query's statistics — a host that never
-        # waits set the pace; one that waits on nearly every step was paced by the GPU
-        "gpu_ms_per_step": pace.get("gpu_ms_per_step"),
-        "pace": dict(pace, note="gpu_ms_per_step excludes each bundle_adjust_frames call's setup / write-back "
-                                "and its first, un-pipelined iteration; ms_per_step is the wall clock of the call"),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": ("synthetic (room0-shaped octree + Replica pinhole RGB-D keyframes, analytic GT); embeddings / "
-                 "decoder / poses trained from random init by %d untimed bundle_adjust_frames iterations on the "
-                 "same keyframes before timing (map_state: %s)" % (args.train_iters_done, "trained"
-                                                                   if args.train_iters_done else "random-init")),
-        "config": {"workload": f"{args.scene}: {args.frames} keyframes x {args.rays_per_frame} rays/iter per GPU, "
-                               f"{tree.count_nodes()} octree nodes, decoder W={args.width}, "
-                               f"{h_m / max(h_r, 1):.1f} samples/hit ray (step {step_size:.5f} m)",
-                   "rays_per_step_per_gpu": rays_per_step, "samples_per_step": h_m, "hit_rays_per_step": h_r,
-                   "aabb_tests_per_step": h_v,
-                   # the sparse decoder: samples whose gradients can be non-zero (the full decoder runs on
-                   # these) and the composited ones (a compositing weight: z < z_min + truncation)
-                   "decoder_kept_fraction": kept / h_m if kept is not None and h_m else None,
-                   "composited_fraction": comp / h_m if comp is not None and h_m else None,
-                   "map_state": "trained" if args.train_iters_done else "random-init",
-                   "train_iterations": args.train_iters_done,
-                   # (iterations so far, composited fraction, kept fraction) after each training chunk
-                   "train_trace": train_trace,
-                   "untrained": untrained,
-                   "parallelism": f"dp{world} (ray-sharded, union-batch loss, "
-                                  f"{dist.get_backend() if world > 1 else 'no'} collectives)"},
+    result.update({
         "roofline": roof_qi,
         "roofline_mfma": {"kernel": f"NRGBD decoder MLP W={w} fwd+bwd (fwd, δ chain, weight gradients)",
                           "bound": "mfma", "achieved": mlp_tf, "peak": MFMA_F32_PEAK_TFS, "unit": "TFLOP/s",
@@ -853,16 +960,17 @@ def main():
                           "fwd_ms": mlp_f_ms, "bwd_ms": mlp_b_ms,
                           "timing": TIMING_NOTE},
         "roofline_bwd_fused" if fused_ib else "roofline_interp_bwd": roof_ib,
-        "path": path_desc,
         "other_path": others if others else "run bench.py --extras for the engine-step and drop-in autograd paths",
         "kernels_ms_overlapped": kt_overlap,
         "kernels_ms_serialised": kt_serial,
         "traffic_kernels": tr.get("kernels"),
-    }
+    })
     if collectives:
         result["collectives"] = collectives
         result["collective_ms_per_step"] = collectives["collective_ms_per_step"]
     log("done timing")
+    if args.dump_outputs:
+        replay_for_dump()
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("CPU baseline")
         result["cpu_baseline"] = cpu_baseline(args, scene, tree, step_size, args.cpu_baseline_seconds)

@@ -378,7 +378,12 @@ class EngineExchange:
             src = dst = buf[in_off:in_off + count]
         if self.world == 1 and not self.force:
             if op == XCH_GATHER_I32:
-                dst.copy_(src)
+                # on the stream the engine produced the operand on (the query's
+                # second half runs on a non-blocking stream of the engine's own:
+                # a copy on torch's current stream is not ordered with it)
+                ctx = torch.cuda.stream(torch.cuda.ExternalStream(stream)) if stream and src.is_cuda else _nullctx()
+                with ctx:
+                    dst.copy_(src)
             return
         if self.nccl:
             ctx = torch.cuda.stream(torch.cuda.ExternalStream(stream)) if stream else _nullctx()

@@ -6,7 +6,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 R=${ROUND:-r02}
-ARGS=${BENCH_ARGS:-}
+ARGS="--full ${BENCH_ARGS:-}"  # the rooflines, the PMC passes and the CPU baseline are behind --full
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 timeout -k 10 400 python bench.py --steps 20 --warmup 5 $ARGS > gpurun_out/${R}_bench.json 2> gpurun_out/${R}_bench.err
