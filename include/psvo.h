@@ -617,6 +617,37 @@ int psvo_debug_lb_helps(int64_t *out3, int reset);
  * always the radix passes, 2: the band forced to miss (its exact fallback).
  * The three give the same picks.  Process-wide. */
 int psvo_debug_set_pixel_draw(int mode);
+/* Tests only: the engine's sample selection (the sparse decoder's
+ * k_select_samples) and its fused compositing pass as the engine calls them,
+ * arguments passed straight through.  Selection: the samples whose gradients
+ * can be non-zero get compact, ray-major indices cidx[s] (-1: dropped) —
+ * class A (composited) at [0, M_A), class B (a loss term only) at
+ * [cap, cap + M_B) (split = 0: every kept sample in class A) —, the classes'
+ * exclusive ray offsets offa / offb [R_hit + 1], and compact copies of the
+ * feat [M][16] / leaf / t / ray_of rows ([2 cap] rows each; class B's rgb_c
+ * [2 cap][3] rows are written 0; src_c, if not null: each kept sample's source
+ * row).  z_vals: rows of stride z_stride >= s_max, read up to ray_ns[r] only.
+ * counts: 10 ints on an 8-byte boundary, zeroed once ([0] M_A, [1] M_B, [2]
+ * flags, [3] composited samples, then three u64 running sums); desc: the
+ * granule count below of u64 words, zeroed once; tag: non-zero, fresh per
+ * launch on the same desc; host_flag may be null. */
+int psvo_debug_select_samples(void *stream, int64_t r_hit, int s_max, float truncation, float max_depth,
+                              const int *offsets, const int *ray_ns, const float *z_vals, int z_stride,
+                              const int *rank_ray, const float *gt_depth, const float *sdf_s, const float *feat,
+                              const int *leaf, const float *t, const int *ray_of, int64_t cap, int split, int *cidx,
+                              int *offa, int *offb, float *feat_c, int *leaf_c, float *t_c, int *ray_of_c,
+                              float *rgb_c, int *src_c, int *counts, uint64_t *desc, uint32_t tag, int *host_flag);
+int64_t psvo_debug_select_granules(int64_t r_hit);
+/* Tests only: psvo_composite_loss with z rows of stride z_stride >= s_max
+ * (read up to ray_ns[r]; MAX_DEPTH implied beyond), partials = 0 to skip the
+ * loss partials, and cidx (null, or the selection's compact index: sample s's
+ * colour and gradients live at row cidx[s], nothing is read or written for
+ * cidx[s] = -1). */
+int psvo_debug_composite_loss(void *stream, int64_t r_hit, int s_max, float truncation, float max_depth,
+                              const int *offsets, const int *ray_ns, const float *z_vals, int z_stride,
+                              const int *rank_ray, const float *gt_rgb, const float *gt_depth, const float *sdf_s,
+                              const float *rgb_s, const float *coef, float *workspace, float *color, float *depth,
+                              float *grad_sdf_s, float *grad_rgb_s, int partials, const int *cidx);
 
 /* Optional HIP-event timing of the roofline regions (on the launch stream). */
 enum { PSVO_TIME_MLP_FWD = 0, PSVO_TIME_MLP_BWD = 1, PSVO_TIME_INTERP_FWD = 2, PSVO_TIME_INTERP_BWD = 3,

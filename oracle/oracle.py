@@ -330,6 +330,33 @@ def relu_margins(params, x):
 
 
 # --------------------------------------------------------------------------
+# Compositing — render_helpers.py:504-556
+# --------------------------------------------------------------------------
+def composite(sdf_s, rgb_s, mask, z, truncation, dtype=torch.float32):
+    """SDF-to-weight compositing of the valid samples' sdf_s [M] / rgb_s [M,3]
+    (ray-major, mask [R,S] marks them) at depths z [R,S]: the padded sdf row
+    (pad 1), the normalised weights, colour, depth, the first sign change
+    "first" [R] and "z_min" [R].  dtype: the arithmetic; the discrete decisions
+    (the sign product sdf[s+1]·sdf[s] < 0, z < z_min + tr) are made from the
+    fp32 values in fp32 for any dtype, as the reference makes them."""
+    R, S = mask.shape
+    sdf = torch.ones(R, S, dtype=dtype).masked_scatter(mask, sdf_s)
+    colour = torch.zeros(R, S, 3, dtype=dtype).masked_scatter(mask.unsqueeze(-1).expand(R, S, 3), rgb_s)
+    valid = mask.float()
+    w = torch.sigmoid(sdf / truncation) * torch.sigmoid(-sdf / truncation)
+    sdf32 = sdf.detach().float()
+    sign = sdf32[:, 1:] * sdf32[:, :-1]
+    first = torch.argmax((sign < 0.0).float(), dim=1)[..., None]
+    z_min = torch.gather(z, 1, first)
+    # the comparison in fp32 as the reference makes it (exact for fp32 z; a dtype=float64 run keeps fp32's
+    # discrete decisions)
+    w = w * (z.float() < z_min.float() + truncation).to(w.dtype) * valid
+    w = w / (w.sum(dim=-1, keepdim=True) + 1e-8)
+    return {"weights": w, "color": (w[..., None] * colour).sum(-2), "depth": (w * z).sum(-1), "sdf": sdf,
+            "first": first[:, 0], "z_min": z_min[:, 0]}
+
+
+# --------------------------------------------------------------------------
 # render_rays — render_helpers.py:351-556
 # --------------------------------------------------------------------------
 def render_rays(rays_o, rays_d, map_states, decoder_params, step_size, voxel_size, truncation, max_distance,
@@ -368,25 +395,13 @@ def render_rays(rays_o, rays_d, map_states, decoder_params, step_size, voxel_siz
         capture["feats"] = feats
         capture["offsets"] = torch.cat([torch.zeros(1, dtype=torch.long), mask.sum(-1).cumsum(0)])
     rgb_s, sdf_s = decoder_forward(decoder_params, feats)
-    R, S = mask.shape
-    sdf = torch.ones(R, S, dtype=dtype).masked_scatter(mask, sdf_s)
-    colour = torch.zeros(R, S, 3, dtype=dtype).masked_scatter(mask.unsqueeze(-1).expand(R, S, 3), rgb_s)
-    valid = mask.float()
-    z = depth
-    w = torch.sigmoid(sdf / truncation) * torch.sigmoid(-sdf / truncation)
-    sign = sdf[:, 1:] * sdf[:, :-1]
-    first = torch.argmax((sign < 0.0).float(), dim=1)[..., None]
-    z_min = torch.gather(z, 1, first)
-    # the comparison in fp32 as the reference makes it (exact for fp32 z; a dtype=float64 run keeps fp32's
-    # discrete decisions)
-    w = w * (z.float() < z_min.float() + truncation).to(w.dtype) * valid
-    w = w / (w.sum(dim=-1, keepdim=True) + 1e-8)
+    comp = composite(sdf_s, rgb_s, mask, depth, truncation, dtype)
     return {
-        "weights": w,
-        "color": (w[..., None] * colour).sum(-2),
-        "depth": (w * z).sum(-1),
-        "z_vals": z,
-        "sdf": sdf,
+        "weights": comp["weights"],
+        "color": comp["color"],
+        "depth": comp["depth"],
+        "z_vals": depth,
+        "sdf": comp["sdf"],
         "ray_mask": ray_mask,
         "samples": samples,
         "sampled_xyz": xyz,

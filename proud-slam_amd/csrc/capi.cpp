@@ -52,6 +52,33 @@ extern "C" int psvo_debug_lb_helps(int64_t *out3, int reset) {
     return psvo::lb_helps_select(out3 + 2, reset != 0);
 }
 
+// tests only: the engine-internal selection / fused compositing entry points, arguments passed straight through
+extern "C" int psvo_debug_select_samples(void *stream, int64_t r_hit, int s_max, float truncation, float max_depth,
+                                         const int *offsets, const int *ray_ns, const float *z_vals, int z_stride,
+                                         const int *rank_ray, const float *gt_depth, const float *sdf_s,
+                                         const float *feat, const int *leaf, const float *t, const int *ray_of,
+                                         int64_t cap, int split, int *cidx, int *offa, int *offb, float *feat_c,
+                                         int *leaf_c, float *t_c, int *ray_of_c, float *rgb_c, int *src_c, int *counts,
+                                         uint64_t *desc, uint32_t tag, int *host_flag) {
+    return psvo::select_samples(psvo::as_stream(stream), r_hit, s_max, truncation, max_depth, offsets, ray_ns, z_vals,
+                                z_stride, rank_ray, gt_depth, sdf_s, feat, leaf, t, ray_of, cap, split != 0, cidx, offa,
+                                offb, feat_c, leaf_c, t_c, ray_of_c, rgb_c, src_c, counts,
+                                reinterpret_cast<unsigned long long *>(desc), tag, host_flag);
+}
+
+extern "C" int64_t psvo_debug_select_granules(int64_t r_hit) { return psvo::select_granules(r_hit); }
+
+extern "C" int psvo_debug_composite_loss(void *stream, int64_t r_hit, int s_max, float truncation, float max_depth,
+                                         const int *offsets, const int *ray_ns, const float *z_vals, int z_stride,
+                                         const int *rank_ray, const float *gt_rgb, const float *gt_depth,
+                                         const float *sdf_s, const float *rgb_s, const float *coef, float *workspace,
+                                         float *color, float *depth, float *grad_sdf_s, float *grad_rgb_s,
+                                         int partials, const int *cidx) {
+    return psvo::composite_loss_z(stream, r_hit, s_max, truncation, max_depth, offsets, ray_ns, z_vals, z_stride,
+                                  rank_ray, gt_rgb, gt_depth, sdf_s, rgb_s, coef, workspace, color, depth, grad_sdf_s,
+                                  grad_rgb_s, partials != 0, cidx);
+}
+
 extern "C" const char *psvo_last_error(void) { return psvo::g_err; }
 
 extern "C" const char *psvo_version(void) { return "psvo 0.1.0 (gfx950)"; }

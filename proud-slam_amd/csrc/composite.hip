@@ -677,7 +677,7 @@ __global__ __launch_bounds__(512) void k_select_samples(int64_t r_hit, int rpw, 
                 const int64_t src = off + s;
                 a.leaf_c[j] = a.leaf[src];
                 a.t_c[j] = a.t[src];
-                a.ray_of_c[j] = (int)r;
+                a.ray_of_c[j] = a.ray_of[src];  // (the engine's rows hold r)
                 if (a.src_c) a.src_c[j] = (int)src;
                 if (a.feat_c) {  // (null: the consumers read row src_c[j] of the step's features)
 #pragma unroll

@@ -85,6 +85,11 @@ _SIGNATURES = {
     "psvo_debug_set_lookback": (_i32, [_i32, _i32, _i32]),
     "psvo_debug_set_pixel_draw": (_i32, [_i32]),
     "psvo_debug_lb_helps": (_i32, [_vp, _i32]),
+    "psvo_debug_select_samples": (_i32, [_vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _i32] + [_vp] * 7
+                                  + [_i64, _i32] + [_vp] * 11 + [ctypes.c_uint32, _vp]),
+    "psvo_debug_select_granules": (_i64, [_i64]),
+    "psvo_debug_composite_loss": (_i32, [_vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _i32] + [_vp] * 11
+                                  + [_i32, _vp]),
     "psvo_engine_queued": (_i32, [_vp]),
     "psvo_map_discard": (_i32, [_vp]),
     "psvo_engine_exchange_words": (_i64, [_i32, _i64, _i64]),

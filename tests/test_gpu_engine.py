@@ -87,7 +87,28 @@ def test_engine_matches_autograd_path():
     eng.close()
 
 
-@pytest.mark.parametrize("padded,sdf_shift", [(False, 0.0), (True, 0.0), (False, 0.5), (True, 0.5)])
+def _surface_setup():
+    """tests/surface_case.py as _setup() hands a case over, plus the rays the
+    engine forms from its poses and sampler noise for them (shared with the
+    oracle, whose counts the selection must reproduce)."""
+    import surface_case as S
+    from psvo import _lib as L
+    from psvo.decoder import Decoder
+    w, tree, emb0, params, ms_cpu = S.surface_case()
+    dec = Decoder(depth=2, width=128, in_dim=16, skips=[], embedder="none").to(DEV)
+    dec.load_state_dict(params)
+    poses, dirs = _frames_of(w, S.RAYS)
+    R = S.FRAMES * S.RAYS
+    ro, rd = torch.empty(R, 3, device=DEV), torch.empty(R, 3, device=DEV)
+    L.call("psvo_pose_rays_frames", L.stream_of(ro.device), R, S.RAYS, poses, dirs, ro, rd)
+    ro_c, rd_c = ro.cpu()[None], rd.cpu()[None]
+    noise = S.sampler_noise(ro_c, rd_c, ms_cpu)
+    _, reg = S.oracle_regime(ro_c, rd_c, noise)
+    return w, tree, emb0, dec, noise, reg
+
+
+@pytest.mark.parametrize("padded,sdf_shift", [(False, 0.0), (True, 0.0), (False, 0.5), (True, 0.5),
+                                              (False, "surface"), (True, "surface")])
 def test_sparse_decoder_matches_dense(padded, sdf_shift):
     """The sparse decoder (the sdf trunk on every sample, the full decoder
     forward and backward on the kept samples only: composited or inside a
@@ -101,15 +122,24 @@ def test_sparse_decoder_matches_dense(padded, sdf_shift):
     zero.  The random decoder's sdf is negative nearly everywhere: the first
     sign change is at the padding (pad 1) and every sample is composited;
     shifted positive (sdf_shift) there is no sign change, z_min is the first
-    sample and most samples are dropped."""
+    sample and most samples are dropped.  "surface" (tests/surface_case.py):
+    the decoder's sdf is the scene's signed distance — the first sign change
+    deep inside most rays, at the padding on some, none on a few, as a trained
+    map has them — on sampler noise shared with the oracle: the selection's
+    composited / kept counts equal the oracle's."""
     from copy import deepcopy
     from psvo.engine import MappingEngine
     from psvo.octree import map_states
-    w, tree, emb0, dec = _setup()
-    dec = deepcopy(dec)
-    with torch.no_grad():
-        dec.sdf_out.bias[0] += sdf_shift
-    n = 512
+    noise, reg = None, None
+    if sdf_shift == "surface":
+        w, tree, emb0, dec, noise, reg = _surface_setup()
+        n = 256
+    else:
+        w, tree, emb0, dec = _setup()
+        dec = deepcopy(dec)
+        with torch.no_grad():
+            dec.sdf_out.bias[0] += sdf_shift
+        n = 512
     poses, dirs = _frames_of(w, n)
     rgb, depth = w.rgb.reshape(-1, 3).to(DEV), w.depth.reshape(-1).to(DEV)
     crit = {"rgb_weight": 0.5, "depth_weight": 1.0, "sdf_weight": 5000.0, "fs_weight": 10.0}
@@ -124,14 +154,18 @@ def test_sparse_decoder_matches_dense(padded, sdf_shift):
         for it in range(2):
             pg = torch.zeros(poses.shape[0], 8, device=DEV)
             loss = eng.step_frames(dirs, n, poses.clone(), torch.zeros_like(poses), torch.zeros_like(poses), [0, 1],
-                                   1e-3, rgb, depth, seed=700 + it, apply_adam=False, pose_grad=pg, want_loss=True)
+                                   1e-3, rgb, depth, seed=700 + it, apply_adam=False, pose_grad=pg, want_loss=True,
+                                   **({} if noise is None else {"noise": noise}))
             torch.cuda.synchronize()
             out.append((float(loss), list(eng.last_stats), eng.grad_flat.cpu().clone(), pg.cpu()))
         if mode == "sparse":
             sel = eng.select_stats()
             m = out[-1][1][4]
             assert sel["steps"] == 2 and 0 < sel["composited"] <= sel["kept"] <= m, (sel, m)
-            if sdf_shift > 0:
+            if reg is not None:  # the oracle's classes on the same rays and draws
+                assert (m, sel["composited"], sel["kept"]) == (reg["M"], reg["composited"], reg["kept"]), (sel, reg)
+                assert (sel["composited_sum"], sel["kept_sum"]) == (2 * reg["composited"], 2 * reg["kept"]), (sel, reg)
+            elif sdf_shift > 0:
                 assert sel["kept"] < 0.8 * m, (sel, m)  # the selection drops samples
         runs[mode] = out
         eng.close()

@@ -71,16 +71,34 @@ def _pose_grad_from_rays(poses, dirs, g_o, g_d, n):
 
 @pytest.mark.parametrize("name", list(F.CONFIGS))
 def test_engine_step_frames_grads_full_size(name):
+    c, w, ms, ms_cpu = F._setup(name)
+    _check_step_frames_grads(c, w, ms, ms_cpu, O.decoder_params_init(c["width"], seed=4))
+
+
+def test_engine_step_frames_grads_surface_case():
+    """The same checks on tests/surface_case.py: a small batch whose decoder
+    sdf is the scene's signed distance, so that the first sign change lies
+    deep inside most rays (the regime of a trained map; the random decoders
+    above cross at the padding)."""
+    import surface_case as S
+    w, tree, emb, params, ms_cpu = S.surface_case()
+    c = dict(scene="room0", frames=S.FRAMES, rays=S.RAYS, step=S.STEP, width=128, max_depth=S.MAX_DEPTH)
+    ms = {k: v.to(DEV) for k, v in ms_cpu.items()}
+    _check_step_frames_grads(c, w, ms, ms_cpu, params)
+
+
+def _check_step_frames_grads(c, w, ms, ms_cpu, params):
+    """One psvo_map_step_frames of config c (scene, frames, rays, step, width,
+    max_depth) on workload w and map states ms (device) / ms_cpu with decoder
+    `params`, stopped before Adam, against the oracle (the module docstring)."""
     from psvo import _lib as L
     from psvo.decoder import Decoder
     from psvo.engine import MappingEngine
-    c, w, ms, ms_cpu = F._setup(name)
     vs = w.scene.voxel_size
     n = c["rays"]
     n_f = c["frames"]
     R = n * n_f
     crit_w = O.SCANNET_CRITERIA if c["scene"] == "scannet0000" else O.REPLICA_CRITERIA
-    params = O.decoder_params_init(c["width"], seed=4)
     poses, dirs = _keyframes(w, c)
     poses_d, dirs_d = poses.to(DEV), dirs.to(DEV)
     ro = torch.empty(R, 3, device=DEV)
