@@ -36,6 +36,8 @@
  *                                 (render_helpers.py:581-596, :668-672)
  *   psvo_map_step                 one bundle_adjust_frames iteration (render_helpers.py:609-672):
  *                                 render_rays + Criterion + backward + both Adam steps
+ *   psvo_render_frame             Tracking.render_debug_images (tracking.py:162-215): render_rays on a
+ *                                 whole frame without autograd + fill_in (render_helpers.py:18) per image
  *   psvo_share_*                  share.ShareData (src/share.py:27-166) served by a BaseManager
  *                                 (voxslam.py:28-33): update_share_data (mapping.py:236-248) /
  *                                 do_tracking (tracking.py:114-125) state exchange, device-resident
@@ -786,6 +788,72 @@ int psvo_map_side_wait(psvo_engine *e, void *stream);
  * formed from) into grad_o / grad_d f32[n_rays, 3], original ray order; rows
  * of rays that hit nothing are undefined.  n_rays must be that step's. */
 int psvo_engine_grad_rays(psvo_engine *e, void *stream, int64_t n_rays, float *grad_o, float *grad_d);
+
+/* ---- whole-frame renderer (csrc/render.hip) ----------------------------
+ * Colour, depth and hit mask of n_rays world rays against the map of `d`
+ * (read only: embeddings, decoder, tree, voxel_size, step_size, truncation,
+ * max_distance; width 128 or 256) — what Tracking.render_debug_images and a
+ * map evaluation at full resolution need — as images: outputs are in ORIGINAL
+ * ray order and the rows of rays that hit nothing are 0 (render_rays' compact
+ * per-hit-ray tensors scattered by fill_in(…, 0)).  color f32[R,3], depth
+ * f32[R], z_min f32[R] or NULL (render_rays' `raw`), mask u8[R] (1: the ray
+ * hit a voxel).  Inference only.
+ *
+ * Result contract: render_helpers.render_rays on the WHOLE ray batch with the
+ * same sampler noise, whatever the tile size —
+ *   noise   the sampler's uniforms are addressed in the whole frame's layout
+ *           [200, K' = ceil(R_hit / 200), max_steps = max ceil(Σ/step) + P] by
+ *           the ray's global hit row: the injected `noise` (f32 of exactly that
+ *           shape, values in [0, 1)) and the draw from `seed` (noise NULL) alike,
+ *           as psvo_track_step.  R_hit, P and max_steps are the frame's, known
+ *           after the traversal: PSVO_RENDER_QUERY_ONLY stops there (outputs
+ *           untouched, stats_out filled up to max_steps), so that a caller can
+ *           size / check its noise before the call that reads it.
+ *   S_max   a ray's padded sdf row has an sdf = 1 element after its last
+ *           sample iff its sample count is below S_max, the maximum over the
+ *           FRAME, not over a tile: a ray whose last sdf is negative crosses
+ *           "into the padding" (z_min = its last depth) unless it attains the
+ *           frame's maximum (then no crossing: z_min = its first depth).  The
+ *           call counts every hit ray's samples in a sampler pre-pass over all
+ *           tiles before any tile is composited (a frame of one tile needs
+ *           none: the tile's maximum is the frame's).
+ *   sums    a ray never straddles tiles and its sums run in its own sample
+ *           order, so every output bit is independent of tile_rays.
+ * Per tile of tile_rays hit rows (<= 0: 16384): the range sampler, the sdf
+ * trunk on every sample, the selection of the composited samples (z < z_min +
+ * truncation), the colour head on those only, compositing and the scatter.
+ * Everything sized by samples lives in a tile workspace of
+ * psvo_render_tile_bytes(tile_rays, max_steps, width) bytes — a function of
+ * the tile alone, not of n_rays; when the frame has fewer hit rays than a
+ * tile the engine allocates for those rows only —, ray-sized buffers
+ * (hit lists, ranks, counts) are whole-frame.  The call allocates (the
+ * engine keeps the buffers) and synchronises `stream` once per frame (the
+ * traversal's statistics) and once more when stats_out is given.  A frame
+ * without a hit ray is not an error: all outputs 0, r_hit 0.  A data-
+ * parallel engine (psvo_engine_set_exchange) is refused: PSVO_E_INVALID. */
+typedef struct psvo_render_opts {
+    int64_t tile_rays; /* hit rows per tile; <= 0: the default */
+    int flags;         /* PSVO_RENDER_* */
+} psvo_render_opts;
+enum { PSVO_RENDER_QUERY_ONLY = 1 };
+enum {
+    PSVO_RENDER_STAT_R_HIT = 0,
+    PSVO_RENDER_STAT_P = 1,
+    PSVO_RENDER_STAT_MAX_STEPS = 2,
+    PSVO_RENDER_STAT_S_MAX = 3,
+    PSVO_RENDER_STAT_M = 4,            /* samples */
+    PSVO_RENDER_STAT_M_COMPOSITED = 5, /* samples the colour head ran on */
+    PSVO_RENDER_STAT_N_TILES = 6,
+    PSVO_RENDER_STAT_RAY_BYTES = 7,    /* whole-frame (ray-sized) workspace */
+    PSVO_RENDER_STAT_TILE_BYTES = 8,   /* = psvo_render_tile_bytes(tile_rays, max_steps, width) */
+    PSVO_RENDER_STAT_WORDS = 9
+};
+int psvo_render_frame(psvo_engine *e, void *stream, const psvo_map_desc *d, int64_t n_rays, const float *rays_o,
+                      const float *rays_d, const float *noise, uint64_t seed, const psvo_render_opts *opts,
+                      float *color, float *depth, float *z_min, uint8_t *mask, int64_t *stats_out);
+/* host only (no GPU): the tile workspace for tile_rays rows of max_steps
+ * sample slots each; -1 on bad arguments */
+int64_t psvo_render_tile_bytes(int64_t tile_rays, int max_steps, int width);
 
 /* ---- octree builder on the device (csrc/octree_gpu.hip) ----------------
  * The same tree as psvo_octree_* (Octree::insert, octree.cpp:104-294: ids in

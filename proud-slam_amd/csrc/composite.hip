@@ -16,6 +16,7 @@
 
 #include "lookback.h"
 #include "psvo_common.h"
+#include "select_common.h"
 
 namespace psvo {
 namespace {
@@ -471,21 +472,9 @@ struct SelectArgs {
                                // the engine reports it at its next host read-back
 };
 
-// the ray's z_min (k_composite_loss's first sign change of the padded sdf row)
-__device__ __forceinline__ float sel_zmin(int lane, int s_max, int ns, int off, const float *z,
-                                          const float *__restrict__ sdf_s) {
-    const int lim = ns < s_max ? ns : s_max;
-    auto sdf_at = [&](int s) { return s < ns ? sdf_s[off + s] : 1.0f; };
-    int first = s_max;
-    for (int s = lane; s < lim; s += 64) {
-        const float v = sdf_at(s);
-        const float v1 = s + 1 < s_max ? sdf_at(s + 1) : 0.f;
-        if (s + 1 < s_max && v1 * v < 0.0f) first = min(first, s);
-    }
-    first = wmin(first);
-    const int f0 = first == s_max ? 0 : first;
-    return f0 < ns ? z[f0] : kMaxDepthFill;
-}
+// the ray's z_min (k_composite_loss's first sign change of the padded sdf
+// row): select_common.h, shared with the frame renderer's selection
+using sel::sel_zmin;
 
 struct SelFlags {
     bool keep, comp;

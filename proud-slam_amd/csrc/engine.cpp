@@ -191,7 +191,14 @@ struct psvo_engine {
     int *host_flags = nullptr;      // coherent pinned: bit 3 = a sample selection gave up its look-back wait
     bool grads_clean = false;       // embedding-gradient buffer known to be zero (Adam zeroes it)
     const float *clean_buf = nullptr;  // ... and which buffer that is
+    psvo::RenderWs *render = nullptr;  // psvo_render_frame's buffers (render.hip owns the type)
 };
+
+// what render.hip needs of the engine (its struct is this file's)
+namespace psvo {
+RenderWs *&engine_render_ws(psvo_engine *e) { return e->render; }
+bool engine_data_parallel(const psvo_engine *e) { return e->x.on(); }
+}  // namespace psvo
 
 using namespace psvo;
 
@@ -710,6 +717,7 @@ extern "C" void psvo_engine_free(psvo_engine *e) {
     if (e->in_ready) (void)hipEventDestroy(e->in_ready);
     if (e->draw_gate) (void)hipEventDestroy(e->draw_gate);
     if (e->host_flags) (void)hipHostFree(e->host_flags);
+    psvo::render_ws_free(e->render);
     delete e;
 }
 

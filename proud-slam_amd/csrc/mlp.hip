@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "interp_fuse.h"
+#include "interp_load.h"
 #include "psvo_common.h"
 
 #ifdef PSVO_STAMPS
@@ -677,15 +678,18 @@ __device__ __forceinline__ void stage8(float *dst, const float *img, int n_float
     for (int c = wave; c < n_floats / 256; c += kF2Waves) glds16(img + (c * 64 + lane) * 4, dst + c * 256);
 }
 
-template <bool H2>
+// IP (the frame renderer, csrc/render.hip): x is interpolated on chip from
+// `ip` (interp_load.h) instead of read from feat
+template <bool H2, bool IP = false>
 __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_fwd2(int64_t m, const float *__restrict__ feat,
                                                             const float *__restrict__ img,
                                                             float *__restrict__ sdf_out, float *__restrict__ rgb_out,
                                                             float *__restrict__ act, uint64_t *__restrict__ masks,
                                                             const int *__restrict__ m_dev,
                                                             const float *__restrict__ h2_rows,
-                                                            const int *__restrict__ h2_src) {
+                                                            const int *__restrict__ h2_src, InterpSrc ip) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    static_assert(!(H2 && IP), "the h2 hand-over reads the step's feature rows");
     if (m_dev) m = __builtin_amdgcn_readfirstlane(*m_dev);  // the sparse decoder's kept samples (<= m)
     // h2_rows: h2 of every sample of the step (k_mlp_sdf2's, the same
     // instructions: the same bits), sample s's row h2_src[s] — the W2 layer
@@ -715,7 +719,10 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_fwd2(int64_t m, const flo
         const int64_t u = u0 + wave;
         const int64_t s = u * kTileS + (lane & 31);
         if (h2_given && u < u1 && s < m) srcn = h2_src[s];
-        load_x(feat, h2_given ? (int64_t)srcn : s, u < u1 && s < m, h, xn);  // (h2 given: feat is the step's rows)
+        if constexpr (IP)
+            iload::load_x_interp(ip, s, u < u1 && s < m, h, xn);
+        else
+            load_x(feat, h2_given ? (int64_t)srcn : s, u < u1 && s < m, h, xn);  // (h2 given: feat is the step's rows)
     }
     stage8(lds, img + kImgVec, kVecPad, wave, lane);
     stage8(lds + kF2W1, img + kImgF1, 2048, wave, lane);
@@ -782,7 +789,10 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_fwd2(int64_t m, const flo
             const int64_t un = u + kF2Waves;
             const int64_t sn = un * kTileS + (lane & 31);
             if (h2_given && un < u1 && sn < m) srcn = h2_src[sn];
-            load_x(feat, h2_given ? (int64_t)srcn : sn, un < u1 && sn < m, h, xn);
+            if constexpr (IP)
+                iload::load_x_interp(ip, sn, un < u1 && sn < m, h, xn);
+            else
+                load_x(feat, h2_given ? (int64_t)srcn : sn, un < u1 && sn < m, h, xn);
         }
         if (!active) {
             ++seq;
@@ -838,10 +848,12 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_fwd2(int64_t m, const flo
 // k_mlp_fwd2's first two layers, so the sdf is bit-identical to its output.
 constexpr int kLdsSdf2 = (kF2Buf0 + 16384) * 4;
 
+// IP: as k_mlp_fwd2's — the frame renderer's trunk pass
+template <bool IP = false>
 __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_sdf2(int64_t m_host, const float *__restrict__ feat,
                                                             const float *__restrict__ img,
                                                             float *__restrict__ sdf_out, const int *__restrict__ m_dev,
-                                                            float *__restrict__ h2_out) {
+                                                            float *__restrict__ h2_out, InterpSrc ip) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // m_dev: the count on the device, m_host the buffers' capacity (a larger
     // batch: nothing here, the host-sized launch after the read-back)
@@ -858,7 +870,10 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_sdf2(int64_t m_host, cons
     float xn[8];
     {
         const int64_t s = (u0 + wave) * kTileS + (lane & 31);
-        load_x(feat, s, u0 + wave < u1 && s < m, h, xn);
+        if constexpr (IP)
+            iload::load_x_interp(ip, s, u0 + wave < u1 && s < m, h, xn);
+        else
+            load_x(feat, s, u0 + wave < u1 && s < m, h, xn);
     }
     stage8(lds, img + kImgVec, kVecPad, wave, lane);
     stage8(lds + kF2W1, img + kImgF1, 2048, wave, lane);
@@ -873,7 +888,10 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_sdf2(int64_t m_host, cons
         for (int i = 0; i < 8; ++i) x[i] = xn[i];
         if (u + kF2Waves < u1) {
             const int64_t sn = (u + kF2Waves) * kTileS + (lane & 31);
-            load_x(feat, sn, sn < m, h, xn);
+            if constexpr (IP)
+                iload::load_x_interp(ip, sn, sn < m, h, xn);
+            else
+                load_x(feat, sn, sn < m, h, xn);
         }
         f32x16 a[kNB], bacc[kNB];
         init_bias(a, lds + kOffB1, h);
@@ -2092,14 +2110,14 @@ static int mlp_fwd_impl(void *stream, int64_t m, int width, const float *feat, c
         PSVO_REQUIRE(act == nullptr && masks == nullptr, "mlp_fwd: the sdf-only forward is inference only");
         static bool attr_s = false;
         if (!attr_s) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mlp_sdf2),
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mlp_sdf2<false>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsSdf2);
             attr_s = true;
         }
         const int64_t tiles = div_up(m, kF2Tile);
         const int grid = (int)(tiles < device_cus() ? tiles : device_cus());
-        psvo::launch(k_mlp_sdf2, dim3(grid), dim3(kF2Threads), kLdsSdf2, st, m, feat, images, sdf, m_dev,
-                     h2 ? h2->out : nullptr);
+        psvo::launch(k_mlp_sdf2<false>, dim3(grid), dim3(kF2Threads), kLdsSdf2, st, m, feat, images, sdf, m_dev,
+                     h2 ? h2->out : nullptr, InterpSrc{});
         return check_launch("mlp_fwd");
     }
     static bool attr2 = false;
@@ -2115,7 +2133,8 @@ static int mlp_fwd_impl(void *stream, int64_t m, int width, const float *feat, c
     PSVO_REQUIRE(!h2 || !h2->rows || h2->src, "mlp_fwd: h2 rows need their source index");
     const bool h2r = h2 && h2->rows;
     psvo::launch(h2r ? k_mlp_fwd2<true> : k_mlp_fwd2<false>, dim3(grid), dim3(kF2Threads), kLdsFwd2, st, m, feat,
-                 images, sdf, rgb, act, masks, m_dev, h2r ? h2->rows : nullptr, h2r ? h2->src : nullptr);
+                 images, sdf, rgb, act, masks, m_dev, h2r ? h2->rows : nullptr, h2r ? h2->src : nullptr,
+                 InterpSrc{});
     return check_launch("mlp_fwd");
 }
 
@@ -2134,6 +2153,32 @@ int mlp_fwd_prepared(void *stream, int64_t m, int width, const float *feat, cons
                      float *act, uint64_t *masks, const int *m_dev, const H2Rows *h2) {
     return mlp_fwd_impl(stream, m, width, feat, w1, b1, w2, b2, w3, b3, w4, b4, w5, b5, images, sdf, rgb, act, masks,
                         true, m_dev, h2);
+}
+// The frame renderer's width-128 decoder passes (csrc/render.hip): the sdf
+// trunk (rgb null) or the whole forward (rgb given) on the m_dev[0] <= m_cap
+// samples of `ip`, their features interpolated in the operand load.  m_cap
+// only sizes the grid (no activations are stored: no CF offsets).
+int mlp_fwd_interp(hipStream_t st, int64_t m_cap, const int *m_dev, const InterpSrc &ip, const float *images,
+                   float *sdf, float *rgb) {
+    PSVO_REQUIRE(m_cap >= 0 && m_dev && images && sdf, "mlp_fwd_interp: bad arguments");
+    if (m_cap == 0) return PSVO_OK;
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mlp_sdf2<true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kLdsSdf2);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mlp_fwd2<false, true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kLdsFwd2);
+        attr = true;
+    }
+    const int64_t tiles = div_up(m_cap, kF2Tile);
+    const int grid = (int)(tiles < device_cus() ? tiles : device_cus());
+    if (rgb == nullptr)
+        psvo::launch(k_mlp_sdf2<true>, dim3(grid), dim3(kF2Threads), kLdsSdf2, st, m_cap, nullptr, images, sdf, m_dev,
+                     nullptr, ip);
+    else
+        psvo::launch(k_mlp_fwd2<false, true>, dim3(grid), dim3(kF2Threads), kLdsFwd2, st, m_cap, nullptr, images, sdf,
+                     rgb, nullptr, nullptr, m_dev, nullptr, nullptr, ip);
+    return check_launch("mlp_fwd_interp");
 }
 }  // namespace psvo
 

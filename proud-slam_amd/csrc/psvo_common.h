@@ -334,6 +334,13 @@ int dec256_bwd(hipStream_t st, int64_t m, const float *feat, const float *images
 
 constexpr int kXchMaxFrames = 64;  // keyframes per psvo_map_step_frames call
 
+// psvo_render_frame (render.hip): its buffers hang off the engine handle
+// (engine.cpp: freed with it) and it refuses a data-parallel engine
+struct RenderWs;
+RenderWs *&engine_render_ws(psvo_engine *e);
+bool engine_data_parallel(const psvo_engine *e);
+void render_ws_free(RenderWs *ws);  // after the device is idle; null: nothing
+
 // ---- in-launch hand-offs between workgroups --------------------------------
 // (cdna_hip_programming.md §6 G16, sc1 form; the per-XCD L2s are not
 // coherent).  Every word another workgroup reads in the same launch is stored

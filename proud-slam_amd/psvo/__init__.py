@@ -8,7 +8,16 @@ modules of the same role.
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib", "octree", "voxel_helpers", "render_helpers", "criterion", "decoder", "synthetic", "dist"]
+__all__ = ["_lib", "octree", "voxel_helpers", "render_helpers", "criterion", "decoder", "synthetic", "dist", "render",
+           "FrameRenderer"]
+
+
+def __getattr__(name):
+    # psvo.FrameRenderer (psvo/render.py), imported on first use like the other submodules
+    if name == "FrameRenderer":
+        from .render import FrameRenderer
+        return FrameRenderer
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def version():

@@ -110,6 +110,8 @@ _SIGNATURES = {
     "psvo_pose_grad_frames": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "psvo_track_step": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _vp, _u64, _i64, _i32, _vp,
                                _vp, _vp]),
+    "psvo_render_frame": (_i32, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "psvo_render_tile_bytes": (_i64, [_i64, _i32, _i32]),
     "psvo_pose_rays": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp]),
     "psvo_mesh_linspace": (_i32, [_i32, _vp]),
     "psvo_mesh_case_table": (_i32, [_vp, _vp]),
