@@ -2079,19 +2079,21 @@ extern "C" int64_t psvo_mlp_mask_words(int64_t m, int width) {
     return width == 128 ? m * 6 : width == 256 ? dec256_mask_words(m) : -1;
 }
 
-static int mlp_fwd_impl(void *stream, int64_t m, int width, const float *feat, const float *w1, const float *b1,
-                            const float *w2, const float *b2, const float *w3, const float *b3, const float *w4,
-                            const float *b4, const float *w5, const float *b5, float *images, float *sdf, float *rgb,
-                            float *act, uint64_t *masks, bool images_ready, const int *m_dev = nullptr,
-                            const H2Rows *h2 = nullptr) {
+// dec: the ten parameter tensors W1, b1, ..., W5, b5, or null: `images` already holds them (mlp_images)
+static MlpParams mlp_params(const float *const *dec) {
+    return MlpParams{dec[0], dec[1], dec[2], dec[3], dec[4], dec[5], dec[6], dec[7], dec[8], dec[9]};
+}
+static int mlp_fwd_impl(void *stream, int64_t m, int width, const float *feat, const float *const *dec, float *images,
+                        float *sdf, float *rgb, float *act, uint64_t *masks, const int *m_dev = nullptr,
+                        const H2Rows *h2 = nullptr) {
     if (width == 256) {
         PSVO_REQUIRE(m >= 0, "mlp_fwd: m < 0");
         PSVO_REQUIRE(images != nullptr, "mlp_fwd: images workspace required (psvo_mlp_image_floats_w floats)");
         PSVO_REQUIRE(act == nullptr || masks != nullptr, "mlp_fwd: act needs masks");
         PSVO_REQUIRE(m <= ((int64_t)1 << 31) / 256, "mlp_fwd: m = %lld too large", (long long)m);
         hipStream_t st = as_stream(stream);
-        if (!images_ready) {
-            const int rc = dec256_images(st, w1, b1, w2, b2, w3, b3, w4, b4, w5, b5, images);
+        if (dec) {
+            const int rc = dec256_images(st, dec, images);
             if (rc) return rc;
         }
         return dec256_fwd(st, m, feat, images, sdf, rgb, act, masks, m_dev);
@@ -2104,8 +2106,10 @@ static int mlp_fwd_impl(void *stream, int64_t m, int width, const float *feat, c
                  (long long)kMaxSamples);
     if (m == 0) return PSVO_OK;
     hipStream_t st = as_stream(stream);
-    MlpParams p{w1, b1, w2, b2, w3, b3, w4, b4, w5, b5};
-    if (!images_ready) psvo::launch(k_mlp_prep, dim3(div_up(kImgTotal, 256)), dim3(256), 0, st, p, images);
+    if (dec) {
+        MlpParams p = mlp_params(dec);
+        psvo::launch(k_mlp_prep, dim3(div_up(kImgTotal, 256)), dim3(256), 0, st, p, images);
+    }
     if (rgb == nullptr) {  // sdf only (inference)
         PSVO_REQUIRE(act == nullptr && masks == nullptr, "mlp_fwd: the sdf-only forward is inference only");
         static bool attr_s = false;
@@ -2139,20 +2143,19 @@ static int mlp_fwd_impl(void *stream, int64_t m, int width, const float *feat, c
 }
 
 namespace psvo {
-int mlp_images(void *stream, int width, const float *w1, const float *b1, const float *w2, const float *b2,
-               const float *w3, const float *b3, const float *w4, const float *b4, const float *w5, const float *b5,
-               float *images) {
-    if (width == 256) return dec256_images(as_stream(stream), w1, b1, w2, b2, w3, b3, w4, b4, w5, b5, images);
-    MlpParams p{w1, b1, w2, b2, w3, b3, w4, b4, w5, b5};
+int mlp_images(void *stream, int width, const float *const *dec, float *images) {
+    if (width == 256) return dec256_images(as_stream(stream), dec, images);
+    MlpParams p = mlp_params(dec);
     psvo::launch(k_mlp_prep, dim3(div_up(kImgTotal, 256)), dim3(256), 0, as_stream(stream), p, images);
     return check_launch("mlp_images");
 }
-int mlp_fwd_prepared(void *stream, int64_t m, int width, const float *feat, const float *w1, const float *b1,
-                     const float *w2, const float *b2, const float *w3, const float *b3, const float *w4,
-                     const float *b4, const float *w5, const float *b5, float *images, float *sdf, float *rgb,
+int mlp_fwd_prepared(void *stream, int64_t m, int width, const float *feat, float *images, float *sdf, float *rgb,
                      float *act, uint64_t *masks, const int *m_dev, const H2Rows *h2) {
-    return mlp_fwd_impl(stream, m, width, feat, w1, b1, w2, b2, w3, b3, w4, b4, w5, b5, images, sdf, rgb, act, masks,
-                        true, m_dev, h2);
+    return mlp_fwd_impl(stream, m, width, feat, nullptr, images, sdf, rgb, act, masks, m_dev, h2);
+}
+int mlp_fwd(void *stream, int64_t m, int width, const float *feat, const float *const *dec, float *images, float *sdf,
+            float *rgb, float *act, uint64_t *masks) {
+    return mlp_fwd_impl(stream, m, width, feat, dec, images, sdf, rgb, act, masks);
 }
 // The frame renderer's width-128 decoder passes (csrc/render.hip): the sdf
 // trunk (rgb null) or the whole forward (rgb given) on the m_dev[0] <= m_cap
@@ -2186,8 +2189,8 @@ extern "C" int psvo_mlp_fwd(void *stream, int64_t m, int width, const float *fea
                             const float *w2, const float *b2, const float *w3, const float *b3, const float *w4,
                             const float *b4, const float *w5, const float *b5, float *images, float *sdf, float *rgb,
                             float *act, uint64_t *masks) {
-    return mlp_fwd_impl(stream, m, width, feat, w1, b1, w2, b2, w3, b3, w4, b4, w5, b5, images, sdf, rgb, act, masks,
-                        false);
+    const float *const dec[10] = {w1, b1, w2, b2, w3, b3, w4, b4, w5, b5};
+    return mlp_fwd_impl(stream, m, width, feat, dec, images, sdf, rgb, act, masks);
 }
 
 static const int kDwRows[5] = {128, 128, 129, 128, 3};
@@ -2228,20 +2231,22 @@ extern "C" int64_t psvo_mlp_workspace_floats_w(int64_t m, int width, int n_split
 // activations and masks.  `workspace`: δ operands + split-K slabs
 // (psvo_mlp_workspace_floats).
 namespace psvo {
-int mlp_bwd(void *stream, int64_t m, int width, const float *feat, const float *w1, const float *b1, const float *w2,
-            const float *b2, const float *w3, const float *b3, const float *w4, const float *b4, const float *w5,
-            const float *b5, const float *images, const float *rgb, const float *act, const uint64_t *masks,
-            const float *g_sdf, const float *g_rgb, float *dfeat, float *gw1, float *gb1, float *gw2, float *gb2,
-            float *gw3, float *gb3, float *gw4, float *gb4, float *gw5, float *gb5, int accumulate, int n_split,
-            float *workspace, hipEvent_t dfeat_ready, const InterpFuse *ip, hipStream_t reduce_stream,
-            const int *m_dev, const TrunkBwd *tb, const int *x_src) {
+int mlp_bwd(void *stream, int64_t m, int width, const float *feat, const float *images, const float *rgb,
+            const float *act, const uint64_t *masks, const float *g_sdf, const float *g_rgb, float *dfeat,
+            float *const *grads, int accumulate, int n_split, float *workspace, hipEvent_t dfeat_ready,
+            const InterpFuse *ip, hipStream_t reduce_stream, const int *m_dev, const TrunkBwd *tb, const int *x_src) {
+    float *gw[5], *gb[5];  // grads = {gW1, gb1, ..., gW5, gb5}
+    for (int l = 0; l < 5; ++l) {
+        gw[l] = grads ? grads[2 * l] : nullptr;
+        gb[l] = grads ? grads[2 * l + 1] : nullptr;
+    }
+    float *const gw1 = gw[0];
     PSVO_REQUIRE(ip == nullptr || ((width == 256 || width == kW) && gw1 != nullptr),
                  "mlp_bwd: the fused interpolation backward needs a fused weight-gradient path");
     if (width == 256) {
         PSVO_REQUIRE(m >= 0, "mlp_bwd: bad sizes");
         PSVO_REQUIRE(images != nullptr && masks != nullptr, "mlp_bwd: images / masks of the training forward required");
         PSVO_REQUIRE(gw1 == nullptr || act != nullptr, "mlp_bwd: weight gradients need the forward's activations");
-        float *gw[5] = {gw1, gw2, gw3, gw4, gw5}, *gb[5] = {gb1, gb2, gb3, gb4, gb5};
         return dec256_bwd(as_stream(stream), m, feat, images, rgb, act, masks, g_sdf, g_rgb, dfeat, gw, gb, accumulate,
                           workspace, dfeat_ready, ip, m_dev);
     }
@@ -2253,7 +2258,6 @@ int mlp_bwd(void *stream, int64_t m, int width, const float *feat, const float *
     hipStream_t st = as_stream(stream);
     DwGrid g;
     int slab_floats;
-    float *gw[5] = {gw1, gw2, gw3, gw4, gw5}, *gb[5] = {gb1, gb2, gb3, gb4, gb5};
     PSVO_REQUIRE(tb == nullptr || (gw1 != nullptr && tb->m_dev && tb->g_sdf && tb->feat),
                  "mlp_bwd: the trunk backward needs the weight-gradient path and its inputs");
     float *slabs_b = nullptr;
@@ -2308,20 +2312,12 @@ int mlp_bwd(void *stream, int64_t m, int width, const float *feat, const float *
         }();
         const bool trunk_last = tb && m > 0;
         bool bound = false;
-        auto bind = [&](bool last) {
-            if (last && bind_env && dfeat_ready) psvo::g_stop_event = dfeat_ready;
-        };
-        auto taken = [&](bool last) {
-            if (last && bind_env && dfeat_ready) {
-                bound = psvo::g_stop_event == nullptr;
-                psvo::g_stop_event = nullptr;
-            }
-        };
+        const hipEvent_t bind_ev = bind_env ? dfeat_ready : nullptr;  // offered to the last kernel only
         if (m > 0) {
-            bind(!trunk_last);
+            psvo::StopBind sb(trunk_last ? nullptr : bind_ev);
             psvo::launch(k_mlp_bwd3<true>, dim3(grid), dim3(kF2Threads), kLdsBwd3, st, m, images, src, g, slabs,
                          ip ? *ip : InterpFuse{}, m_dev);
-            taken(!trunk_last);
+            bound = sb.consumed();
             const int rc = check_launch("mlp_bwd3");
             if (rc) return rc;
         } else if (hipMemsetAsync(slabs, 0, (size_t)slab_floats * sizeof(float), st) != hipSuccess) {
@@ -2338,11 +2334,11 @@ int mlp_bwd(void *stream, int64_t m, int width, const float *feat, const float *
             }
             slabs_b = slabs + slab_floats;
             PSVO_REQUIRE(!tb->h2 || tb->src, "mlp_bwd: the trunk's h2 rows need their source index");
-            bind(true);
+            psvo::StopBind sb(bind_ev);
             psvo::launch(tb->h2 ? k_mlp_trunk_fb<true> : k_mlp_trunk_fb<false>, dim3(grid), dim3(kF2Threads), kLdsTrunk,
                          st, tb->m_dev, images, tb->g_sdf, tb->feat, g, slabs_b, tb->ip ? *tb->ip : InterpFuse{},
                          tb->h2, tb->src);
-            taken(true);
+            bound = sb.consumed();
             const int rc = check_launch("mlp_trunk_fb");
             if (rc) return rc;
         }
@@ -2373,7 +2369,8 @@ extern "C" int psvo_mlp_bwd(void *stream, int64_t m, int width, const float *fea
                             const float *act, const uint64_t *masks, const float *g_sdf, const float *g_rgb, float *dfeat, float *gw1,
                             float *gb1, float *gw2, float *gb2, float *gw3, float *gb3, float *gw4, float *gb4,
                             float *gw5, float *gb5, int accumulate, int n_split, float *workspace) {
-    return psvo::mlp_bwd(stream, m, width, feat, w1, b1, w2, b2, w3, b3, w4, b4, w5, b5, images, rgb, act, masks,
-                         g_sdf, g_rgb, dfeat, gw1, gb1, gw2, gb2, gw3, gb3, gw4, gb4, gw5, gb5, accumulate, n_split,
-                         workspace, nullptr);
+    // (the weights are not read: `images` holds them)
+    float *const grads[10] = {gw1, gb1, gw2, gb2, gw3, gb3, gw4, gb4, gw5, gb5};
+    return psvo::mlp_bwd(stream, m, width, feat, images, rgb, act, masks, g_sdf, g_rgb, dfeat, grads, accumulate,
+                         n_split, workspace, nullptr);
 }

@@ -1080,9 +1080,8 @@ int64_t dec256_workspace_floats(int64_t m) {
     return dec256_tiles16(m) * 16 * (256 + 256 + 144 + 256 + 16) + slab;
 }
 
-int dec256_images(hipStream_t st, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
-                  const float *b3, const float *w4, const float *b4, const float *w5, const float *b5, float *images) {
-    Params p{w1, b1, w2, b2, w3, b3, w4, b4, w5, b5};
+int dec256_images(hipStream_t st, const float *const *dec, float *images) {
+    Params p{dec[0], dec[1], dec[2], dec[3], dec[4], dec[5], dec[6], dec[7], dec[8], dec[9]};
     psvo::launch(k_dec256_prep, dim3(div_up(kImgTotal, 256)), dim3(256), 0, st, p, images);
     return check_launch("dec256_images");
 }
@@ -1170,11 +1169,10 @@ int dec256_bwd(hipStream_t st, int64_t m, const float *feat, const float *images
             const char *v = getenv("PSVO_BIND_DFEAT");
             return !(v && v[0] == '0');
         }();
-        if (bind_env && dfeat_ready) psvo::g_stop_event = dfeat_ready;
+        psvo::StopBind sb(bind_env ? dfeat_ready : nullptr);
         psvo::launch(k_dec256_bwd, dim3(grid_for(n_tiles)), dim3(kCThreads), lds, st, m, n_tiles, images, rgb,
                      g_sdf, g_rgb, a, d, dfeat, ip ? *ip : InterpFuse{}, m_dev);
-        bound = bind_env && dfeat_ready && psvo::g_stop_event == nullptr;
-        psvo::g_stop_event = nullptr;
+        bound = sb.consumed();
         const int rc = check_launch("dec256_bwd");
         if (rc) return rc;
     }

@@ -91,6 +91,34 @@ inline void launch(void (*k)(KArgs...), dim3 grid, dim3 block, uint32_t lds, hip
     if (late) (void)hipEventRecord(late, st);
 }
 
+// The binding above, scoped to one launch: `ev` (null: nothing to bind) is
+// offered to the next psvo::launch on this thread and all three words are
+// cleared when the scope ends, whichever way it ends — an event never stays
+// behind for a later, unrelated launch.
+struct __attribute__((visibility("hidden"))) StopBind {
+    explicit StopBind(hipEvent_t ev, bool share = false) : ev_(ev) {
+        g_stop_event = ev;
+        g_stop_share = share;
+        g_stop_bound = nullptr;
+    }
+    ~StopBind() {
+        g_stop_event = nullptr;
+        g_stop_share = false;
+        g_stop_bound = nullptr;
+    }
+    StopBind(const StopBind &) = delete;
+    StopBind &operator=(const StopBind &) = delete;
+    // a launch took the event: it marks that launch's completion (bound to
+    // the dispatch, shared with the clock's, or recorded right after it);
+    // false: nothing was launched, the caller records the event itself
+    bool consumed() const { return ev_ && g_stop_event == nullptr; }
+    // the event that marks the completion (the clock's own when shared)
+    hipEvent_t bound() const { return g_stop_bound; }
+
+  private:
+    hipEvent_t ev_;
+};
+
 // Set the thread-local error message; returns `code` for tail calls.
 int set_error(int code, const char *fmt, ...);
 
@@ -238,9 +266,14 @@ constexpr int kDistWordsPerRank = 8;
 // word 0 of a rank's second-gather words: its S_max, with this bit set when
 // it did not count its rows (no GT depths given to its query)
 constexpr int kDistNotCounted = 1 << 30;
-// PSVO_STAT_FLAGS bit set by k_dist_smax when some rank did not count: every
-// rank then counts in its step (one decision for all ranks, so all issue the
-// same collectives)
+// The bits of a query's PSVO_STAT_FLAGS word (the engine turns the first
+// four into errors at the read-back):
+constexpr int kStatFlagDfsOverflow = 1;      // the octree is deeper than the traversal's DFS stack
+constexpr int kStatFlagSamplerOverflow = 2;  // a ray needs more than the sampler rows' max_steps
+constexpr int kStatFlagUnionOverflow = 4;    // data parallel: the union batch exceeds max_rays_global
+constexpr int kLbFlagTimeout = 8;            // a look-back wait was abandoned (lookback.h's bug trap)
+// set by k_dist_smax when some rank did not count: every rank then counts in
+// its step (one decision for all ranks, so all issue the same collectives)
 constexpr int PSVO_FLAG_UNION_UNCOUNTED = 16;
 int dist_slot0_rows(int64_t max_rays_global);
 int dist_count_words(int max_rays_rank);
@@ -318,8 +351,8 @@ int64_t dec256_image_floats();
 int64_t dec256_act_floats(int64_t m);
 int64_t dec256_mask_words(int64_t m);
 int64_t dec256_workspace_floats(int64_t m);
-int dec256_images(hipStream_t st, const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
-                  const float *b3, const float *w4, const float *b4, const float *w5, const float *b5, float *images);
+// dec: the ten parameter tensors W1, b1, ..., W5, b5 (psvo_map_desc::dec)
+int dec256_images(hipStream_t st, const float *const *dec, float *images);
 // rgb, act and masks all null: the sdf trunk only (k_dec256_trunk, the same sdf
 // bits).  m_dev: the sample count read on the device (<= m; buffers sized for m)
 int dec256_fwd(hipStream_t st, int64_t m, const float *feat, const float *images, float *sdf, float *rgb, float *act,
@@ -426,13 +459,14 @@ struct TrunkBwd {
     const int *src = nullptr;   // the W2 layer is read instead of recomputed; feat then holds the
                                 // step's rows too (x of sample s: row src[s])
 };
-int mlp_bwd(void *stream, int64_t m, int width, const float *feat, const float *w1, const float *b1, const float *w2,
-            const float *b2, const float *w3, const float *b3, const float *w4, const float *b4, const float *w5,
-            const float *b5, const float *images, const float *rgb, const float *act, const uint64_t *masks,
-            const float *g_sdf, const float *g_rgb, float *dfeat, float *gw1, float *gb1, float *gw2, float *gb2,
-            float *gw3, float *gb3, float *gw4, float *gb4, float *gw5, float *gb5, int accumulate, int n_split,
-            float *workspace, hipEvent_t dfeat_ready, const InterpFuse *ip = nullptr,
-            hipStream_t reduce_stream = nullptr, const int *m_dev = nullptr, const TrunkBwd *tb = nullptr,
+// grads: the ten parameter gradients gW1, gb1, ..., gW5, gb5 (the order of
+// psvo_map_desc::dec); a null array or null entries: the δ chain / dfeat only
+// (frozen decoder).  The weights themselves are not read: `images` holds them.
+int mlp_bwd(void *stream, int64_t m, int width, const float *feat, const float *images, const float *rgb,
+            const float *act, const uint64_t *masks, const float *g_sdf, const float *g_rgb, float *dfeat,
+            float *const *grads, int accumulate, int n_split, float *workspace, hipEvent_t dfeat_ready,
+            const InterpFuse *ip = nullptr, hipStream_t reduce_stream = nullptr, const int *m_dev = nullptr,
+            const TrunkBwd *tb = nullptr,
             const int *x_src = nullptr);  // x_src (width 128): sample s's x is row x_src[s] of feat
 // whether mlp_bwd can take `ip` for this width (the fused width-128 backward is built and selected)
 bool mlp_bwd_fuses_interp(int width);
@@ -444,9 +478,8 @@ bool mlp_bwd_split_tail(int width);
 // the decoder's LDS operand images (k_mlp_prep) on their own, and
 // psvo_mlp_fwd without rebuilding them (the engine prepares them on its aux
 // stream beside the sampler / interpolation kernels)
-int mlp_images(void *stream, int width, const float *w1, const float *b1, const float *w2, const float *b2,
-               const float *w3, const float *b3, const float *w4, const float *b4, const float *w5, const float *b5,
-               float *images);
+// (dec: the ten parameter tensors W1, b1, ..., W5, b5, psvo_map_desc::dec)
+int mlp_images(void *stream, int width, const float *const *dec, float *images);
 // the sparse decoder's h2 hand-over (width 128): the sdf-only forward
 // (rgb == nullptr) writes every sample's h2 as row-major rows into `out`
 // [m][128]; the full forward (k_mlp_fwd2) reads sample s's h2 from row src[s]
@@ -458,11 +491,12 @@ struct H2Rows {
     const float *rows = nullptr;
     const int *src = nullptr;
 };
-int mlp_fwd_prepared(void *stream, int64_t m, int width, const float *feat, const float *w1, const float *b1,
-                     const float *w2, const float *b2, const float *w3, const float *b3, const float *w4,
-                     const float *b4, const float *w5, const float *b5, float *images, float *sdf, float *rgb,
+int mlp_fwd_prepared(void *stream, int64_t m, int width, const float *feat, float *images, float *sdf, float *rgb,
                      float *act, uint64_t *masks, const int *m_dev = nullptr,
                      const H2Rows *h2 = nullptr);  // m_dev: as mlp_bwd (width 128)
+// psvo_mlp_fwd with the decoder as one array (it builds the images first)
+int mlp_fwd(void *stream, int64_t m, int width, const float *feat, const float *const *dec, float *images, float *sdf,
+            float *rgb, float *act, uint64_t *masks);
 
 }  // namespace psvo
 

@@ -343,7 +343,8 @@ extern "C" int psvo_render_frame(psvo_engine *e, void *stream, const psvo_map_de
     if (hipMemcpyAsync(ws->host, stats, PSVO_STAT_WORDS * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
         return set_error(PSVO_E_LAUNCH, "render_frame: statistics read-back failed");
-    if (ws->host[PSVO_STAT_FLAGS] & 1) return set_error(PSVO_E_OVERFLOW, "render_frame: traversal stack overflow");
+    if (ws->host[PSVO_STAT_FLAGS] & kStatFlagDfsOverflow)
+        return set_error(PSVO_E_OVERFLOW, "render_frame: traversal stack overflow");
     const int P = ws->host[PSVO_STAT_P];
     const int64_t r_hit = ws->host[PSVO_STAT_R_HIT];
     const int max_steps = ws->host[PSVO_STAT_MAX_CEIL] + P;
@@ -380,8 +381,7 @@ extern "C" int psvo_render_frame(psvo_engine *e, void *stream, const psvo_map_de
     // ---- decoder operand images (once per frame)
     const int64_t img_floats = psvo_mlp_image_floats_w(d->width);
     R_BUF(float, images, kRImages, (size_t)img_floats * sizeof(float));
-    R_CALL(mlp_images(stream, d->width, d->dec[0], d->dec[1], d->dec[2], d->dec[3], d->dec[4], d->dec[5], d->dec[6],
-                      d->dec[7], d->dec[8], d->dec[9], images));
+    R_CALL(mlp_images(stream, d->width, d->dec, images));
     const int n_tiles = (int)so[PSVO_RENDER_STAT_N_TILES];
     auto sample_tile = [&](int64_t row0, int64_t n) {
         return psvo_sample_rays_range(stream, row0, n, rows, max_steps, rank_ray, hit_idx, hit_t0, hit_t1, ray_dsum,

@@ -916,7 +916,7 @@ __global__ __launch_bounds__(64 * kIsWaves) void k_intersect_sorted(int64_t n_ra
             atomicAdd(stats + PSVO_STAT_ROUNDS, rd);
         }
         if (sps) atomicAdd(stats + PSVO_STAT_SPILLS, sps);
-        if (ov) atomicOr(stats + 7, 1);
+        if (ov) atomicOr(stats + PSVO_STAT_FLAGS, kStatFlagDfsOverflow);
     }
     if (!lb_desc) return;
     // wave 0: the workgroup's aggregate → its exclusive prefix (lookback.h);
@@ -1759,7 +1759,8 @@ __device__ __forceinline__ int sample_fused_ray(int64_t row_begin, int64_t n_row
     const int64_t n_own = n_rows < 0 ? (int64_t)r_hit - row_begin : n_rows;
     if (i >= r_hit || il >= n_own || il >= r_hit_cap || P <= 0) return -1;
     // (look-back mode: the last workgroup derives this flag; no atomics on `stats`)
-    if (!tl.desc && max_steps > max_steps_cap && lane == 0 && il == 0) atomicOr(stats + PSVO_STAT_FLAGS, 2);
+    if (!tl.desc && max_steps > max_steps_cap && lane == 0 && il == 0)
+        atomicOr(stats + PSVO_STAT_FLAGS, kStatFlagSamplerOverflow);
     const int kp = (r_hit + kSamplerG - 1) / kSamplerG;
     const int b = i / kp;
     const int j = i - b * kp;
@@ -1775,7 +1776,7 @@ __device__ __forceinline__ int sample_fused_ray(int64_t row_begin, int64_t n_row
                    (int64_t)orig * kMaxHits, dsum};
     if (slot0) {
         if (c >= slot0_nch) {  // the exchanged table covers slot0_nch launch chunks
-            if (lane == 0) atomicOr(stats + PSVO_STAT_FLAGS, 4);
+            if (lane == 0) atomicOr(stats + PSVO_STAT_FLAGS, kStatFlagUnionOverflow);
             return -1;
         }
         rows.slot0 = slot0;
@@ -1972,7 +1973,7 @@ __device__ void smp_lb_finish(int n, const SmpLb &lb, int *__restrict__ stats, c
     const int max_steps = __shfl(st_word, PSVO_STAT_MAX_CEIL, kWave) + __shfl(st_word, PSVO_STAT_P, kWave);
     if (lane < PSVO_STAT_WORDS) {
         int v = lane == PSVO_STAT_S_MAX ? smax : lane == PSVO_STAT_M ? tot : st_word;
-        if (lane == PSVO_STAT_FLAGS && n > 0 && max_steps > max_steps_cap) v |= 2;
+        if (lane == PSVO_STAT_FLAGS && n > 0 && max_steps > max_steps_cap) v |= kStatFlagSamplerOverflow;
         if (lane == PSVO_STAT_FLAGS && !ok) v |= kLbFlagTimeout;
         if (lane < kStatQuery) stats[lane] = 0;  // ready for the query set's next use (no memset launch)
         if (tl.host) stat_to_host(tl.host, lane, v, tl.seq);
