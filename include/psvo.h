@@ -875,6 +875,47 @@ int psvo_dtree_export(void *tree, void *stream, float voxel_size, float *voxels,
 /* hit[i·corners + j] = leaf at voxel i's corner j exists (corners 1: has_voxel,
  * 8: the corner keys try_insert counts, octree.cpp:381-474) */
 int psvo_dtree_probe(void *tree, void *stream, const int *vox, int64_t n, int corners, int *hit);
+/* advances iff an insert (voxel list or depth frame) created a node or turned
+ * a leaf SURFACE: exported arrays stay valid while it is unchanged */
+uint64_t psvo_dtree_generation(void *tree);
+
+/* ---- a depth frame into the device octree -----------------
+ * Mapping.create_voxels_pointcloud (mapping.py:258-295) in one call.  The
+ * voxel key of pixel p, pinned operation by operation (BLAS summation order
+ * is no contract): v = dirs_cam[p] · depth[p] (frame.py:69), world_k =
+ * ((v0·R[k][0] + v1·R[k][1]) + v2·R[k][2]) + t[k] with every product and sum
+ * rounded to fp32 on its own (no FMA), key_k = (int32) of torch's floor
+ * division of world_k by voxel_size (c10 div_floor_floating).  A pixel is
+ * valid iff depth > 0 (frame.py:71) and its three quotients are finite and
+ * inside int32; depth > 0 without such a key is counted as skipped.
+ * depth f32[n_pix], dirs_cam f32[n_pix,3] (frame.rays_d), pose34 f32[12]
+ * row-major [R | t]: device pointers.
+ * keys i32[n_pix,3] (0 where not valid) and valid u8[n_pix]; no tree involved */
+int psvo_depth_voxel_keys(void *stream, int64_t n_pix, const float *depth, const float *dirs_cam,
+                          const float *pose34, float voxel_size, int *keys, uint8_t *valid);
+
+enum { PSVO_FRAME_STAT_VALID = 0,     /* pixels with depth > 0 and a representable key */
+       PSVO_FRAME_STAT_SKIPPED = 1,   /* depth > 0 but non-finite / out of int32 */
+       PSVO_FRAME_STAT_DISTINCT = 2,  /* distinct voxels in the frame (by the 21 coordinate bits the tree reads) */
+       PSVO_FRAME_STAT_NEW = 3,       /* of those, not yet a SURFACE leaf */
+       PSVO_FRAME_STAT_CREATED = 4,   /* nodes created */
+       PSVO_FRAME_STAT_WORKSPACE_BYTES = 5,
+       PSVO_FRAME_STAT_WORDS = 8 };
+
+/* host only (no GPU): the frame workspace a tree keeps for h x w frames
+ * (keys, frame-local set, survivor list); -1 on bad arguments */
+int64_t psvo_dtree_frame_workspace_bytes(int h, int w);
+
+/* The tree becomes, bit for bit, what psvo_dtree_insert of every valid
+ * pixel's key in row-major pixel order gives; only the first occurrence of
+ * each voxel that has no SURFACE leaf yet goes through the builder (its walk
+ * counter advances by 8 per such voxel).  tree NULL, h or w <= 0, h·w > 2^24,
+ * a null image or voxel_size <= 0: PSVO_E_INVALID before any device call.  A
+ * frame without a valid pixel leaves the tree untouched (zero stats).
+ * Synchronises `stream` once to read the survivor count.
+ * stats_out: PSVO_FRAME_STAT_WORDS host words, or NULL */
+int psvo_dtree_insert_depth(void *tree, void *stream, int h, int w, const float *depth, const float *dirs_cam,
+                            const float *pose34, float voxel_size, int64_t *stats_out /* host, or NULL */);
 
 /* ---- tracker <-> mapper state exchange (csrc/share.cpp) ----------------
  * A POSIX shared-memory block `name` ("/…") holds a robust process-shared

@@ -433,22 +433,6 @@ __global__ __launch_bounds__(256) void k_point_feat(int64_t n, float voxel_size,
     feat[s * 4 + q] = gather_interp(p, vertex_idx + v * 8, emb, q);
 }
 
-// torch's floor division of floats (c10 div_floor_floating): the vertex's
-// voxel coordinate `points // voxel_size` (mesh_util.py:115)
-__device__ __forceinline__ float div_floor(float a, float b) {
-    const float mod = fmodf(a, b);
-    float div = (a - mod) / b;
-    if (mod != 0.f && ((b < 0.f) != (mod < 0.f))) div -= 1.0f;
-    float fl;
-    if (div != 0.f) {
-        fl = floorf(div);
-        if (div - fl > 0.5f) fl += 1.0f;
-    } else {
-        fl = copysignf(0.f, a / b);
-    }
-    return fl;
-}
-
 // open-addressing map voxel min corner → SURFACE row (keys from the
 // exported voxels, integral floats)
 __device__ __forceinline__ uint32_t key_hash(int x, int y, int z) {

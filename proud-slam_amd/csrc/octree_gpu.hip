@@ -91,6 +91,9 @@ struct DtTable {
 
 constexpr int kDtMaxProbe = 256;
 constexpr uint64_t kDtNoSlot = ~0ull;
+// k_dt_walk's status word: a probe run overflowed (the batch is redone in a
+// larger table); some leaf became SURFACE (the generation advances)
+constexpr int kDtWalkOverflow = 1, kDtWalkChanged = 2;
 
 // slot of `k`, inserting it if absent; kDtNoSlot if the probe run exceeds
 // kDtMaxProbe (the host grows the table and redoes the batch)
@@ -170,14 +173,18 @@ __global__ void k_dt_walk(DtTable t, const int *__restrict__ vox, int64_t n_walk
     const int x = vox[3 * i] + kDtIncX[j], y = vox[3 * i + 1] + kDtIncY[j], z = vox[3 * i + 2] + kDtIncZ[j];
     const uint64_t s = dt_insert(t, dt_key(x, y, z, d, D));
     if (s == kDtNoSlot) {
-        *overflow = 1;
+        if (!(__atomic_load_n(overflow, __ATOMIC_RELAXED) & kDtWalkOverflow)) atomicOr(overflow, kDtWalkOverflow);
         return;
     }
     // the shallow keys are shared by nearly every walk: a plain read first
     // keeps the same-address atomics (which serialise) to the few that can win
     const unsigned wv = w_base + (unsigned)w;
     if (wv < __atomic_load_n(t.minw + s, __ATOMIC_RELAXED)) atomicMin(t.minw + s, wv);
-    if (d == D && j == 0 && !(__atomic_load_n(t.flags + s, __ATOMIC_RELAXED) & 1u)) atomicOr(t.flags + s, 1u);
+    if (d == D && j == 0 && !(__atomic_load_n(t.flags + s, __ATOMIC_RELAXED) & 1u)) {
+        atomicOr(t.flags + s, 1u);
+        // a leaf that was not SURFACE before (new, or a FEATURE leaf promoted): the tree changes
+        if (!(__atomic_load_n(overflow, __ATOMIC_RELAXED) & kDtWalkChanged)) atomicOr(overflow, kDtWalkChanged);
+    }
 }
 
 // 2. creator flags (w, d order)
@@ -353,6 +360,220 @@ __global__ void k_dt_probe(DtTable t, const int *__restrict__ vox, int64_t n, in
     hit[e] = (s >= 0 && t.id[s] >= 0) ? 1 : 0;
 }
 
+// ---- one depth frame into the tree (psvo_dtree_insert_depth) ----
+// Mapping.create_voxels_pointcloud (mapping.py:258-295) without the per-pixel
+// insert: the pixels' voxel keys, the first occurrence of every distinct key
+// (a frame-local hash set holding the minimum pixel index), of those the ones
+// the tree has no SURFACE leaf for, compacted in pixel order — the list the
+// walk … link stages above then insert.  A later duplicate and a voxel that
+// is already a SURFACE leaf change nothing in Octree::insert, so the tree is
+// the one raw insertion of every valid pixel builds.
+
+// state of a pixel: 0 no depth, 1 valid, 2 depth > 0 but no int32 key
+// World point ((v0·R[k][0] + v1·R[k][1]) + v2·R[k][2]) + t[k] of v = dir · depth,
+// every product and sum rounded to fp32 on its own (no contraction), then
+// torch's floor division by the voxel size.
+__device__ __forceinline__ int fi_pixel_key(float depth, float d0, float d1, float d2, const float *P, float voxel_size,
+                                            int *key) {
+    // plain operators with contraction off for this block: __fmul_rn / __fadd_rn
+    // are `x * y` / `x + y` in the HIP headers and inline into contractible code
+#pragma clang fp contract(off)
+    key[0] = key[1] = key[2] = 0;
+    if (!(depth > 0.f)) return 0;
+    const float v0 = d0 * depth, v1 = d1 * depth, v2 = d2 * depth;
+    bool ok = true;
+    int q[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float p0 = v0 * P[4 * k], p1 = v1 * P[4 * k + 1], p2 = v2 * P[4 * k + 2];
+        const float wk = ((p0 + p1) + p2) + P[4 * k + 3];
+        const float f = div_floor(wk, voxel_size);
+        // torch's .int() is defined only for a finite quotient inside int32
+        const bool in = isfinite(wk) && f >= -2147483648.f && f < 2147483648.f;
+        ok = ok && in;
+        q[k] = in ? (int)f : 0;
+    }
+    if (!ok) return 2;
+    key[0] = q[0], key[1] = q[1], key[2] = q[2];
+    return 1;
+}
+
+// keys i32[n,3] and valid u8[n]; four consecutive pixels per lane, 16-B loads
+// and stores when every pointer allows (vec); stats (or null): += valid, skipped
+__global__ __launch_bounds__(256) void k_fi_keys(int64_t n, const float *__restrict__ depth,
+                                                 const float *__restrict__ dirs, const float *__restrict__ pose,
+                                                 float voxel_size, int *__restrict__ keys,
+                                                 uint8_t *__restrict__ valid, int vec, int *__restrict__ stats) {
+    float P[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) P[i] = pose[i];
+    const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    int n_valid = 0, n_skipped = 0;
+    if (p0 < n) {
+        const bool full = vec && p0 + 4 <= n;
+        float dep[4] = {0.f, 0.f, 0.f, 0.f}, dir[12];
+        if (full) {
+            const float4 a = *reinterpret_cast<const float4 *>(depth + p0);
+            const float4 *dv = reinterpret_cast<const float4 *>(dirs + 3 * p0);
+            const float4 b0 = dv[0], b1 = dv[1], b2 = dv[2];
+            dep[0] = a.x, dep[1] = a.y, dep[2] = a.z, dep[3] = a.w;
+            dir[0] = b0.x, dir[1] = b0.y, dir[2] = b0.z, dir[3] = b0.w;
+            dir[4] = b1.x, dir[5] = b1.y, dir[6] = b1.z, dir[7] = b1.w;
+            dir[8] = b2.x, dir[9] = b2.y, dir[10] = b2.z, dir[11] = b2.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const bool in = p0 + j < n;
+                dep[j] = in ? depth[p0 + j] : 0.f;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) dir[3 * j + k] = in ? dirs[3 * (p0 + j) + k] : 0.f;
+            }
+        }
+        int key[12];
+        uint8_t ok[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int s = fi_pixel_key(dep[j], dir[3 * j], dir[3 * j + 1], dir[3 * j + 2], P, voxel_size, key + 3 * j);
+            ok[j] = s == 1;
+            n_valid += s == 1;
+            n_skipped += s == 2;
+        }
+        if (full) {
+            int4 *kv = reinterpret_cast<int4 *>(keys + 3 * p0);
+            kv[0] = make_int4(key[0], key[1], key[2], key[3]);
+            kv[1] = make_int4(key[4], key[5], key[6], key[7]);
+            kv[2] = make_int4(key[8], key[9], key[10], key[11]);
+            *reinterpret_cast<uchar4 *>(valid + p0) = make_uchar4(ok[0], ok[1], ok[2], ok[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (p0 + j >= n) break;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) keys[3 * (p0 + j) + k] = key[3 * j + k];
+                valid[p0 + j] = ok[j];
+            }
+        }
+    }
+    if (stats) {
+#pragma unroll
+        for (int sh = 32; sh > 0; sh >>= 1) {
+            n_valid += __shfl_xor(n_valid, sh, 64);
+            n_skipped += __shfl_xor(n_skipped, sh, 64);
+        }
+        if ((threadIdx.x & 63) == 0) {
+            if (n_valid) atomicAdd(stats + PSVO_FRAME_STAT_VALID, n_valid);
+            if (n_skipped) atomicAdd(stats + PSVO_FRAME_STAT_SKIPPED, n_skipped);
+        }
+    }
+}
+
+// The frame's set: open addressing with linear probing over `mask + 1` slots
+// of {key, minimum pixel index}, at least two slots per pixel, so a probe
+// always meets the key or an empty slot (the bound below only keeps a
+// corrupted set from spinning).  The walk, the hash key and the node code
+// read the low 21 bits of a coordinate (dt_key, dt_morton, dt_spread3), so
+// those 63 bits identify the voxel.
+struct FiSet {
+    unsigned long long *key;
+    unsigned int *minp;
+    uint64_t mask;
+};
+__device__ __forceinline__ uint64_t fi_pack(const int *k) {
+    return ((uint64_t)k[0] & 0x1fffffull) | ((uint64_t)k[1] & 0x1fffffull) << 21 | ((uint64_t)k[2] & 0x1fffffull) << 42;
+}
+// head of a run: a valid pixel whose previous pixel is not a valid pixel with
+// the same key; every other valid pixel is a duplicate and never touches the set
+__device__ __forceinline__ bool fi_head(const int *__restrict__ keys, const uint8_t *__restrict__ valid, int64_t p,
+                                        uint64_t &pk) {
+    if (!valid[p]) return false;
+    pk = fi_pack(keys + 3 * p);
+    return !(p > 0 && valid[p - 1] && fi_pack(keys + 3 * (p - 1)) == pk);
+}
+
+__global__ __launch_bounds__(256) void k_fi_set(FiSet s, const int *__restrict__ keys,
+                                                const uint8_t *__restrict__ valid, int64_t n) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t pk;
+    if (p >= n || !fi_head(keys, valid, p, pk)) return;
+    uint64_t i = dt_hash(pk) & s.mask;
+    for (uint64_t probe = 0; probe <= s.mask; ++probe) {
+        unsigned long long cur = s.key[i];
+        if (cur == kEmptyKey) {
+            cur = atomicCAS(s.key + i, kEmptyKey, (unsigned long long)pk);
+            if (cur == kEmptyKey) cur = pk;
+        }
+        if (cur == pk) {
+            if ((unsigned)p < __atomic_load_n(s.minp + i, __ATOMIC_RELAXED)) atomicMin(s.minp + i, (unsigned)p);
+            return;
+        }
+        i = (i + 1) & s.mask;
+    }
+}
+
+// survivors: run heads that hold their key's minimum pixel index and whose
+// voxel is not a SURFACE leaf yet.  lrank[p] = rank among the block's
+// survivors in pixel order (ballot + mbcnt in the wave, a scan of the 16 wave
+// totals), −1 for the others; totals[block] = the block's survivors.
+__global__ __launch_bounds__(1024) void k_fi_flag(FiSet s, DtTable t, DtNodes nd, int D, const int *__restrict__ keys,
+                                                  const uint8_t *__restrict__ valid, int64_t n,
+                                                  int *__restrict__ lrank, int *__restrict__ totals,
+                                                  int *__restrict__ stats) {
+    __shared__ int ws[16];
+    const int64_t p = (int64_t)blockIdx.x * 1024 + threadIdx.x;
+    bool first = false, surv = false;
+    uint64_t pk;
+    if (p < n && fi_head(keys, valid, p, pk)) {
+        uint64_t i = dt_hash(pk) & s.mask;
+        for (uint64_t probe = 0; probe <= s.mask; ++probe) {
+            const unsigned long long cur = s.key[i];
+            if (cur == pk) {
+                first = s.minp[i] == (unsigned)p;
+                break;
+            }
+            if (cur == kEmptyKey) break;
+            i = (i + 1) & s.mask;
+        }
+        if (first) {
+            const int *k = keys + 3 * p;
+            const int64_t sl = dt_find(t, dt_key(k[0], k[1], k[2], D, D));
+            const int id = sl >= 0 ? t.id[sl] : -1;
+            surv = !(id >= 0 && nd.type[id] == kDtSurface);
+        }
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(surv), bal_first = __ballot(first);
+    const int in_wave = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
+    if (lane == 0) {
+        ws[w] = __popcll(bal);
+        if (bal_first) atomicAdd(stats + PSVO_FRAME_STAT_DISTINCT, __popcll(bal_first));
+    }
+    __syncthreads();
+    if (w == 0) {
+        int v = lane < 16 ? ws[lane] : 0;
+#pragma unroll
+        for (int sh = 1; sh < 16; sh <<= 1) {
+            const int u = __shfl_up(v, sh, 64);
+            if (lane >= sh) v += u;
+        }
+        if (lane < 16) ws[lane] = v;
+    }
+    __syncthreads();
+    if (p < n) lrank[p] = surv ? (w > 0 ? ws[w - 1] : 0) + in_wave : -1;
+    if (threadIdx.x == 1023) totals[blockIdx.x] = ws[15];
+}
+
+// totals: the blocks' exclusive offsets (k_dt_scan_totals)
+__global__ __launch_bounds__(1024) void k_fi_compact(const int *__restrict__ keys, const int *__restrict__ lrank,
+                                                     const int *__restrict__ totals, int64_t n, int *__restrict__ list) {
+    const int64_t p = (int64_t)blockIdx.x * 1024 + threadIdx.x;
+    if (p >= n) return;
+    const int r = lrank[p];
+    if (r < 0) return;
+    const int64_t o = (int64_t)totals[blockIdx.x] + r;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) list[3 * o + k] = keys[3 * p + k];
+}
+
 }  // namespace
 }  // namespace psvo
 
@@ -366,6 +587,9 @@ struct psvo_dtree {
     DtNodes nd{};
     int *scratch = nullptr;  // flags | ranks | totals | sum | overflow
     int64_t scratch_n = 0;
+    uint64_t generation = 0;  // advances when an insert created a node or promoted a leaf
+    char *frame_ws = nullptr;  // psvo_dtree_insert_depth's workspace (FrameLayout), reused across frames
+    int64_t frame_ws_bytes = 0;
 };
 
 namespace {
@@ -468,14 +692,15 @@ extern "C" void psvo_dtree_free(void *tree) {
     (void)hipFree(tr->t.id);
     (void)hipFree(tr->t.flags);
     (void)hipFree(tr->scratch);
+    (void)hipFree(tr->frame_ws);
     delete tr;
 }
 
-extern "C" int psvo_dtree_insert(void *tree, void *stream, const int *vox, int64_t n) {
-    psvo_dtree *tr = static_cast<psvo_dtree *>(tree);
-    PSVO_REQUIRE(tr != nullptr && n >= 0 && (n == 0 || vox != nullptr), "dtree_insert: bad arguments");
-    if (n == 0) return PSVO_OK;
-    hipStream_t st = as_stream(stream);
+namespace {
+
+// one batch of voxels (n > 0) through the walk … link stages; *created: the
+// nodes it made, *changed: it made one or turned a leaf SURFACE
+int dt_insert_batch(psvo_dtree *tr, hipStream_t st, const int *vox, int64_t n, int *created_out, bool *changed) {
     const int64_t n_walks = n * 8, ne = n_walks * tr->D;
     PSVO_REQUIRE(ne < (int64_t)1 << 31 && (uint64_t)tr->w_next + (uint64_t)n_walks < 0xffffffffull,
                  "dtree_insert: batch too large (%lld voxels)", (long long)n);
@@ -494,18 +719,18 @@ extern "C" int psvo_dtree_insert(void *tree, void *stream, const int *vox, int64
     // for that and grow (rehash from the node arrays, batch redone) if a
     // probe run still overflows
     uint64_t want = 2 * (uint64_t)(tr->count + 3 * n);
+    int ov = 0;
     for (int attempt = 0;; ++attempt) {
         if (want > tr->t.mask + 1) {
             int rc = dt_alloc_table(tr, st, want);
             if (rc) return rc;
         }
-        int ov = 0;
         (void)hipMemsetAsync(overflow, 0, sizeof(int), st);
         psvo::launch(k_dt_walk, g, b, 0, st, tr->t, vox, n_walks, tr->D, tr->w_next, overflow);
         if (hipMemcpyAsync(&ov, overflow, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
             return set_error(PSVO_E_LAUNCH, "dtree_insert: walk failed (%s)", hipGetErrorString(hipGetLastError()));
-        if (!ov) break;
+        if (!(ov & kDtWalkOverflow)) break;
         if (attempt >= 6) return set_error(PSVO_E_OVERFLOW, "dtree_insert: hash table overflow");
         want = 4 * (tr->t.mask + 1);
         int rc = dt_alloc_table(tr, st, want);
@@ -530,7 +755,139 @@ extern "C" int psvo_dtree_insert(void *tree, void *stream, const int *vox, int64
     psvo::launch(k_dt_link, g, b, 0, st, tr->t, tr->nd, vox, n_walks, tr->D, tr->size, flag);
     tr->count += created;
     tr->w_next += (unsigned)n_walks;
+    *created_out = created;
+    *changed = created > 0 || (ov & kDtWalkChanged);
     return check_launch("dtree_insert");
+}
+
+// psvo_dtree_insert_depth's workspace: a host-only function of (h, w)
+struct FrameLayout {
+    int64_t n, slots, nb;
+    int64_t keys, valid, set_key, set_min, lrank, totals, stats, list, bytes;  // byte offsets, 256-B aligned
+};
+constexpr int64_t kFrameMaxPix = (int64_t)1 << 24;
+bool frame_layout(int h, int w, FrameLayout &L) {
+    if (h <= 0 || w <= 0 || (int64_t)h * w > kFrameMaxPix) return false;
+    L.n = (int64_t)h * w;
+    L.slots = 64;
+    while (L.slots < 2 * L.n) L.slots <<= 1;  // load <= 1/2 even if every pixel is its own voxel
+    L.nb = (L.n + 1023) / 1024;
+    int64_t o = 0;
+    auto take = [&o](int64_t bytes) {
+        const int64_t at = o;
+        o += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    L.keys = take(L.n * 3 * sizeof(int));
+    L.valid = take(L.n);
+    L.set_key = take(L.slots * sizeof(unsigned long long));  // set_key | set_min: one memset clears both
+    L.set_min = take(L.slots * sizeof(unsigned));
+    L.lrank = take(L.n * sizeof(int));
+    L.totals = take(L.nb * sizeof(int));
+    L.stats = take(PSVO_FRAME_STAT_WORDS * sizeof(int));
+    L.list = take(L.n * 3 * sizeof(int));
+    L.bytes = o;
+    return true;
+}
+
+bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+void launch_frame_keys(hipStream_t st, int64_t n, const float *depth, const float *dirs, const float *pose,
+                       float voxel_size, int *keys, uint8_t *valid, int *stats) {
+    const int vec = aligned16(depth) && aligned16(dirs) && aligned16(keys) && (reinterpret_cast<uintptr_t>(valid) & 3) == 0;
+    psvo::launch(k_fi_keys, dim3(div_up(div_up(n, 4), 256)), dim3(256), 0, st, n, depth, dirs, pose, voxel_size, keys,
+                 valid, vec, stats);
+}
+
+}  // namespace
+
+extern "C" int psvo_dtree_insert(void *tree, void *stream, const int *vox, int64_t n) {
+    psvo_dtree *tr = static_cast<psvo_dtree *>(tree);
+    PSVO_REQUIRE(tr != nullptr && n >= 0 && (n == 0 || vox != nullptr), "dtree_insert: bad arguments");
+    if (n == 0) return PSVO_OK;
+    int created = 0;
+    bool changed = false;
+    const int rc = dt_insert_batch(tr, as_stream(stream), vox, n, &created, &changed);
+    if (rc == PSVO_OK && changed) ++tr->generation;
+    return rc;
+}
+
+extern "C" uint64_t psvo_dtree_generation(void *tree) {
+    const psvo_dtree *tr = static_cast<const psvo_dtree *>(tree);
+    return tr ? tr->generation : 0;
+}
+
+extern "C" int psvo_depth_voxel_keys(void *stream, int64_t n_pix, const float *depth, const float *dirs_cam,
+                                     const float *pose34, float voxel_size, int *keys, uint8_t *valid) {
+    PSVO_REQUIRE(n_pix >= 0 && n_pix <= (int64_t)1 << 31 && voxel_size > 0.f, "depth_voxel_keys: bad arguments");
+    if (n_pix == 0) return PSVO_OK;
+    PSVO_REQUIRE(depth && dirs_cam && pose34 && keys && valid, "depth_voxel_keys: null pointer");
+    launch_frame_keys(as_stream(stream), n_pix, depth, dirs_cam, pose34, voxel_size, keys, valid, nullptr);
+    return check_launch("depth_voxel_keys");
+}
+
+extern "C" int64_t psvo_dtree_frame_workspace_bytes(int h, int w) {
+    FrameLayout L;
+    return frame_layout(h, w, L) ? L.bytes : -1;
+}
+
+extern "C" int psvo_dtree_insert_depth(void *tree, void *stream, int h, int w, const float *depth,
+                                       const float *dirs_cam, const float *pose34, float voxel_size,
+                                       int64_t *stats_out) {
+    psvo_dtree *tr = static_cast<psvo_dtree *>(tree);
+    FrameLayout L;
+    PSVO_REQUIRE(tr != nullptr && frame_layout(h, w, L) && depth && dirs_cam && pose34 && voxel_size > 0.f,
+                 "dtree_insert_depth: bad arguments (frames of 1 .. 2^24 pixels, device images, voxel_size > 0)");
+    hipStream_t st = as_stream(stream);
+    if (L.bytes > tr->frame_ws_bytes) {
+        (void)hipStreamSynchronize(st);
+        (void)hipFree(tr->frame_ws);
+        tr->frame_ws = nullptr;
+        tr->frame_ws_bytes = 0;
+        if (hipMalloc(&tr->frame_ws, L.bytes) != hipSuccess)
+            return set_error(PSVO_E_LAUNCH, "dtree_insert_depth: out of device memory (%lld bytes)", (long long)L.bytes);
+        tr->frame_ws_bytes = L.bytes;
+    }
+    char *ws = tr->frame_ws;
+    int *keys = reinterpret_cast<int *>(ws + L.keys), *lrank = reinterpret_cast<int *>(ws + L.lrank),
+        *totals = reinterpret_cast<int *>(ws + L.totals), *stats = reinterpret_cast<int *>(ws + L.stats),
+        *list = reinterpret_cast<int *>(ws + L.list);
+    uint8_t *valid = reinterpret_cast<uint8_t *>(ws + L.valid);
+    FiSet set{reinterpret_cast<unsigned long long *>(ws + L.set_key), reinterpret_cast<unsigned int *>(ws + L.set_min),
+              (uint64_t)L.slots - 1};
+    // empty key and "no pixel yet" are both all ones
+    (void)hipMemsetAsync(ws + L.set_key, 0xff, L.set_min - L.set_key + L.slots * sizeof(unsigned), st);
+    (void)hipMemsetAsync(stats, 0, PSVO_FRAME_STAT_WORDS * sizeof(int), st);
+    launch_frame_keys(st, L.n, depth, dirs_cam, pose34, voxel_size, keys, valid, stats);
+    psvo::launch(k_fi_set, dim3(div_up(L.n, 256)), dim3(256), 0, st, set, keys, valid, L.n);
+    psvo::launch(k_fi_flag, dim3(L.nb), dim3(1024), 0, st, set, tr->t, tr->nd, tr->D, keys, valid, L.n, lrank, totals,
+                 stats);
+    psvo::launch(k_dt_scan_totals, dim3(1), dim3(1024), 0, st, totals, L.nb, stats + PSVO_FRAME_STAT_NEW);
+    psvo::launch(k_fi_compact, dim3(L.nb), dim3(1024), 0, st, keys, lrank, totals, L.n, list);
+    int hs[PSVO_FRAME_STAT_WORDS] = {};
+    if (hipMemcpyAsync(hs, stats, sizeof(hs), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return set_error(PSVO_E_LAUNCH, "dtree_insert_depth: frame pass failed (%s)", hipGetErrorString(hipGetLastError()));
+    const int64_t n_new = hs[PSVO_FRAME_STAT_NEW];
+    int64_t created = 0;
+    // the stages index a batch's (walk, depth) pairs in 32 bits: a list of
+    // survivors longer than that goes in as consecutive batches, which is the
+    // same sequential insertion
+    const int64_t per_batch = (((int64_t)1 << 31) - 1) / (8 * tr->D);
+    for (int64_t at = 0; at < n_new; at += per_batch) {
+        int made = 0;
+        bool changed = false;
+        const int rc = dt_insert_batch(tr, st, list + 3 * at, n_new - at < per_batch ? n_new - at : per_batch, &made, &changed);
+        if (rc) return rc;
+        created += made;
+        if (changed) ++tr->generation;  // every survivor lacks a SURFACE leaf: inserting it makes or promotes one
+    }
+    if (stats_out) {
+        for (int i = 0; i < PSVO_FRAME_STAT_WORDS; ++i) stats_out[i] = hs[i];
+        stats_out[PSVO_FRAME_STAT_CREATED] = created;
+        stats_out[PSVO_FRAME_STAT_WORKSPACE_BYTES] = L.bytes;
+    }
+    return PSVO_OK;
 }
 
 extern "C" int64_t psvo_dtree_count(void *tree) {

@@ -229,6 +229,24 @@ __device__ __forceinline__ void adam_elem(float &p, float g, float &m, float &v,
     v = vi;
 }
 
+// torch's floor division of floats (c10 div_floor_floating): a vertex's voxel
+// coordinate `points // voxel_size` (mesh_util.py:115, mesh.hip) and a depth
+// pixel's voxel key torch.div(points, voxel_size, rounding_mode='floor')
+// (mapping.py:264, octree_gpu.hip k_fi_keys) — one copy, so both give torch's bits
+__device__ __forceinline__ float div_floor(float a, float b) {
+    const float mod = fmodf(a, b);
+    float div = (a - mod) / b;
+    if (mod != 0.f && ((b < 0.f) != (mod < 0.f))) div -= 1.0f;
+    float fl;
+    if (div != 0.f) {
+        fl = floorf(div);
+        if (div - fl > 0.5f) fl += 1.0f;
+    } else {
+        fl = copysignf(0.f, a / b);
+    }
+    return fl;
+}
+
 // the bundle-adjust pose work (pose.hip), over each frame's rays directly
 // (ray_rank[r] >= 0: a hit ray; the engine's sums — one fixed order for both
 // calls): the frames' pose gradients (k_pose_grad_rays), and the

@@ -23,6 +23,40 @@ def _zeros_view(n, k, c, device="cpu"):
     return torch.zeros((1, 1, 1), dtype=torch.float32, device=device).expand(n, k, c)
 
 
+FRAME_STATS = ("valid", "skipped", "distinct", "new", "created", "workspace_bytes")  # PSVO_FRAME_STAT_*
+
+
+def _pose34(pose):
+    p = torch.as_tensor(pose)
+    if p.dim() != 2 or p.shape[1] != 4 or p.shape[0] not in (3, 4):
+        raise RuntimeError(f"pose must be a 4 x 4 or 3 x 4 tensor (got {tuple(p.shape)})")
+    return p[:3].to(torch.float32)
+
+
+def _frame_shapes(depth, rays_d):
+    if depth.dim() != 2 or rays_d.dim() != 3 or tuple(rays_d.shape) != (depth.shape[0], depth.shape[1], 3):
+        raise RuntimeError(f"depth must be [H, W] and rays_d [H, W, 3] (got {tuple(depth.shape)}, {tuple(rays_d.shape)})")
+
+
+def depth_voxel_keys_cpu(depth, rays_d, pose, voxel_size):
+    """psvo_depth_voxel_keys' contract (include/psvo.h) in torch-CPU
+    elementwise ops: (keys i32[H·W, 3], valid bool[H·W], skipped).  The sum
+    runs left to right over separately rounded products — no matmul, whose
+    summation order is the BLAS's business."""
+    _frame_shapes(depth, rays_d)
+    d = depth.detach().to("cpu", torch.float32).reshape(-1)
+    r = rays_d.detach().to("cpu", torch.float32).reshape(-1, 3)
+    P = _pose34(pose).detach().cpu()
+    v = r * d[:, None]  # frame.py:69
+    world = torch.stack([((v[:, 0] * P[k, 0] + v[:, 1] * P[k, 1]) + v[:, 2] * P[k, 2]) + P[k, 3] for k in range(3)], -1)
+    q = torch.div(world, torch.tensor(float(voxel_size), dtype=torch.float32), rounding_mode="floor")  # mapping.py:264
+    has = d > 0  # frame.py:71
+    ok = (torch.isfinite(world) & (q >= -2.0 ** 31) & (q < 2.0 ** 31)).all(-1)  # where .int() is defined
+    valid = has & ok
+    keys = torch.where(valid[:, None], q, torch.zeros_like(q)).to(torch.int32)
+    return keys, valid, int((has & ~ok).sum())
+
+
 class Octree:
     def __init__(self):
         self._h = None
@@ -58,6 +92,28 @@ class Octree:
         a = self._as_int3(pts)
         self._inserted.append(a)
         L.call("psvo_octree_insert", self._h, a.ctypes.data_as(L._vp), int(a.shape[0]))
+
+    def insert_frame(self, depth, rays_d, pose, voxel_size=None):
+        """DeviceOctree.insert_frame on the CPU builder: the same keys
+        (depth_voxel_keys_cpu), the first occurrence of each voxel in pixel
+        order, then insert — the tree raw insertion of every valid pixel
+        builds (a later duplicate creates and promotes nothing).  Returns the
+        same statistics."""
+        self._check()
+        vs = self.voxel_size if voxel_size is None else float(voxel_size)
+        if not vs > 0:
+            raise RuntimeError("voxel_size must be positive")
+        keys, valid, skipped = depth_voxel_keys_cpu(depth, rays_d, pose, vs)
+        k = keys[valid].numpy()
+        # the walk reads the low 21 bits of a coordinate: they identify the voxel
+        packed = ((k[:, 0].astype(np.int64) & 0x1fffff) | (k[:, 1].astype(np.int64) & 0x1fffff) << 21
+                  | (k[:, 2].astype(np.int64) & 0x1fffff) << 42)
+        first = np.sort(np.unique(packed, return_index=True)[1])
+        nodes, leaves = self.count_nodes(), self.count_leaf_nodes()
+        if first.size:
+            self.insert(k[first])
+        return {"valid": int(k.shape[0]), "skipped": skipped, "distinct": int(first.size),
+                "new": self.count_leaf_nodes() - leaves, "created": self.count_nodes() - nodes, "workspace_bytes": 0}
 
     def try_insert(self, pts):
         self._check()
@@ -140,6 +196,7 @@ class DeviceOctree:
     def __init__(self, device="cuda"):
         self.device = torch.device(device)
         self._h = None
+        self._states = None  # map_states' last export: ((generation, voxel_size, device), arrays)
         self.size = self.feat_dim = self.max_num = 0
         self.voxel_size = 0.0
 
@@ -165,6 +222,31 @@ class DeviceOctree:
         self._check()
         v = self._vox(pts)
         L.call("psvo_dtree_insert", self._h, L.stream_of(self.device), v, v.shape[0])
+
+    def insert_frame(self, depth, rays_d, pose, voxel_size=None):
+        """Mapping.create_voxels_pointcloud (mapping.py:258-295) in one call
+        (psvo_dtree_insert_depth): depth [H, W], rays_d [H, W, 3]
+        (frame.rays_d), pose 4 x 4 or 3 x 4 camera-to-world; voxel_size
+        defaults to the tree's.  The tree becomes what insert() of every
+        valid pixel's voxel gives; only voxels without a SURFACE leaf go
+        through the builder.  Returns the statistics (FRAME_STATS);
+        `generation` tells whether the map changed."""
+        self._check()
+        _frame_shapes(depth, rays_d)
+        vs = self.voxel_size if voxel_size is None else float(voxel_size)
+        d = depth.to(device=self.device, dtype=torch.float32).contiguous()
+        r = rays_d.to(device=self.device, dtype=torch.float32).contiguous()
+        p = _pose34(pose).to(self.device).contiguous()
+        stats = np.zeros(8, np.int64)  # PSVO_FRAME_STAT_WORDS
+        L.call("psvo_dtree_insert_depth", self._h, L.stream_of(self.device), int(d.shape[0]), int(d.shape[1]), d, r, p,
+               vs, stats.ctypes.data_as(L._vp))
+        return {k: int(stats[i]) for i, k in enumerate(FRAME_STATS)}
+
+    @property
+    def generation(self):
+        """Advances iff an insert created a node or turned a leaf SURFACE."""
+        self._check()
+        return int(L.lib().psvo_dtree_generation(self._h))
 
     def count_nodes(self):
         self._check()
@@ -232,6 +314,7 @@ class DeviceOctree:
         if self._h:
             L.lib().psvo_dtree_free(self._h)
         self._h = None
+        self._states = None
 
     def __del__(self):
         try:
@@ -243,15 +326,21 @@ class DeviceOctree:
 def map_states(tree: Octree, embeddings: torch.Tensor, voxel_size: float, device=None):
     """Mapping.update_grid_pcd_features (mapping.py:300-406) without the
     pointcloud fields: centres, [N,9] structure, vertex ids on `device`.  A
-    DeviceOctree hands over its device arrays directly."""
+    DeviceOctree hands over its device arrays directly, and the very same
+    tensors again while its `generation` is unchanged — the engine keys its
+    packed tree on them (MapEngine._map_key), so a frame that added nothing
+    rebuilds nothing."""
     if isinstance(tree, DeviceOctree):
-        centres, structure, features = tree.render_arrays(voxel_size)
+        dev = torch.device(device if device is not None else embeddings.device)
+        key = (tree.generation, float(voxel_size), dev)
+        if tree._states is None or tree._states[0] != key:
+            tree._states = (key, tuple(a.to(dev) for a in tree.render_arrays(voxel_size)))
+        centres, structure, features = tree._states[1]
         n = centres.shape[0]
-        dev = device if device is not None else embeddings.device
         return {
-            "voxel_vertex_idx": features.to(dev),
-            "voxel_center_xyz": centres.to(dev),
-            "voxel_structure": structure.to(dev),
+            "voxel_vertex_idx": features,
+            "voxel_center_xyz": centres,
+            "voxel_structure": structure,
             "voxel_vertex_emb": embeddings,
             "pointclouds_xyz": _zeros_view(n, tree.max_num, 4),
             "pointclouds_color": _zeros_view(n, tree.max_num, 3),
