@@ -584,8 +584,13 @@ int psvo_map_discard(psvo_engine *e);
  * PSVO_PATH_DENSE_DECODER — the width-128 decoder forward and backward on
  * every sample (the tracking / autograd form) instead of the sparse decoder
  * (the sdf trunk on every sample, the full decoder on the samples whose
- * gradients can be non-zero: composited or inside a loss mask). */
-enum { PSVO_PATH_QUERY_SPLIT = 1, PSVO_PATH_PADDED = 2, PSVO_PATH_DENSE_DECODER = 4 };
+ * gradients can be non-zero: composited or inside a loss mask);
+ * PSVO_PATH_INTERP_PASS — the device-sized forward's interpolation as a pass
+ * of its own (k_interp_fwd, then the sdf trunk reading the feature rows: the
+ * host-sized and width-256 form) instead of inside the width-128 trunk's
+ * operand load.  An engine is created with this bit set when the environment
+ * has PSVO_INTERP_PASS=1 (an A/B of the two schedules from one binary). */
+enum { PSVO_PATH_QUERY_SPLIT = 1, PSVO_PATH_PADDED = 2, PSVO_PATH_DENSE_DECODER = 4, PSVO_PATH_INTERP_PASS = 8 };
 int psvo_engine_set_paths(psvo_engine *e, int paths);   /* with no query queued */
 
 /* The sparse decoder's sample selection (synchronises `stream`, which must
@@ -640,6 +645,20 @@ int psvo_debug_select_samples(void *stream, int64_t r_hit, int s_max, float trun
                               int *offa, int *offb, float *feat_c, int *leaf_c, float *t_c, int *ray_of_c,
                               float *rgb_c, int *src_c, int *counts, uint64_t *desc, uint32_t tag, int *host_flag);
 int64_t psvo_debug_select_granules(int64_t r_hit);
+/* Tests only: the mapping step's device-sized sdf trunk (width 128) on its
+ * own, on the m_dev[0] samples (leaf, t, ray_of; ray_index[ray_of[s]] the
+ * sample's ray) within buffers of m_cap rows.  fused = 1: the engine's one
+ * launch, the trunk interpolating in its operand load; fused = 0: the
+ * interpolation pass followed by the plain trunk.  Both leave sdf [m_cap], h2
+ * [m_cap][128] and feat [m_cap][16], the same bits; rows >= m_dev[0], and every
+ * row when m_dev[0] > m_cap, are not written.  images: psvo_mlp_image_floats
+ * floats of workspace, built here from the ten parameter tensors. */
+int psvo_debug_trunk_interp(void *stream, int fused, int64_t m_cap, const int *m_dev, const int *leaf, const float *t,
+                            const int *ray_of, const int *ray_index, const float *rays_o, const float *rays_d,
+                            const float *centres, const int *vertex_idx, const float *emb, float voxel_size,
+                            const float *w1, const float *b1, const float *w2, const float *b2, const float *w3,
+                            const float *b3, const float *w4, const float *b4, const float *w5, const float *b5,
+                            float *images, float *sdf, float *h2, float *feat);
 /* Tests only: psvo_composite_loss with z rows of stride z_stride >= s_max
  * (read up to ray_ns[r]; MAX_DEPTH implied beyond), partials = 0 to skip the
  * loss partials, and cidx (null, or the selection's compact index: sample s's

@@ -277,6 +277,10 @@ int pose_adam(hipStream_t st, const psvo_map_desc *d, const PoseAdam &pa) {
 
 extern "C" psvo_engine *psvo_engine_new(void) {
     psvo_engine *e = new psvo_engine();
+    // PSVO_INTERP_PASS=1: engines start with the separate interpolation pass
+    // (psvo_engine_set_paths replaces the whole mask)
+    const char *ipass = getenv("PSVO_INTERP_PASS");
+    if (ipass && ipass[0] == '1') e->paths |= PSVO_PATH_INTERP_PASS;
     for (auto &q : e->qs)
         if (query_set_init(q) != PSVO_OK) {
             psvo_engine_free(e);
@@ -320,7 +324,9 @@ extern "C" int psvo_engine_set_exchange(psvo_engine *e, int rank, int world, int
 }
 
 extern "C" int psvo_engine_set_paths(psvo_engine *e, int paths) {
-    PSVO_REQUIRE(e && (paths & ~(PSVO_PATH_QUERY_SPLIT | PSVO_PATH_PADDED | PSVO_PATH_DENSE_DECODER)) == 0, "engine_set_paths: bad arguments");
+    PSVO_REQUIRE(e && (paths & ~(PSVO_PATH_QUERY_SPLIT | PSVO_PATH_PADDED | PSVO_PATH_DENSE_DECODER |
+                               PSVO_PATH_INTERP_PASS)) == 0,
+                 "engine_set_paths: bad arguments");
     PSVO_REQUIRE(e->q_count == 0, "engine_set_paths: queries are queued");
     e->paths = paths;
     return PSVO_OK;

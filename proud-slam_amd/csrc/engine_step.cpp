@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "engine_internal.h"
+#include "interp_load.h"
 
 using namespace psvo;
 using namespace psvo::eng;
@@ -171,7 +172,8 @@ int prepare_images(const MapRender &c, Images &im) {
     return PSVO_OK;
 }
 
-// The device-sized forward: the interpolation and the sdf trunk queued
+// The device-sized forward: the interpolation and the sdf trunk (width 128:
+// one kernel, the trunk interpolating in its operand load) queued
 // BEFORE the host waits for the query's statistics, sized on the device
 // (the sampler's M, kMDev) within a capacity grown from earlier batches —
 // the GPU runs them straight after the sampler instead of after the
@@ -208,17 +210,33 @@ int device_forward(const MapRender &c, const Images &im, Render &o, EarlyFwd &ef
         ef.h2 = he;
     }
     ENG_CALL(join_adam(e, st, c.who, 2000.0));
-    mark(e, st, PSVO_TIME_INTERP_FWD, 0);
-    ENG_CALL(psvo::interp_fwd_dev(st, m_early, m_dev, d->voxel_size, static_cast<const int *>(qset.a.p[kLeafQ]),
-                                  static_cast<const float *>(qset.a.p[kTQ]),
-                                  static_cast<const int *>(qset.a.p[kRayOfQ]),
-                                  static_cast<const int *>(qset.a.p[kRankRay]), c.rays_o, c.rays_d, d->centres,
-                                  d->vertex_idx, d->emb, ef.feat));
-    mark(e, st, PSVO_TIME_INTERP_FWD, 1);
+    const int *leaf_q = static_cast<const int *>(qset.a.p[kLeafQ]);
+    const float *t_q = static_cast<const float *>(qset.a.p[kTQ]);
+    const int *ray_of_q = static_cast<const int *>(qset.a.p[kRayOfQ]);
+    const int *rank_ray = static_cast<const int *>(qset.a.p[kRankRay]);
+    // width 128: the trunk interpolates in its operand load and leaves the
+    // feature rows itself (k_mlp_sdf2<true, true>: k_interp_fwd's bits) — no
+    // separate pass over the samples between the sampler and the trunk, and no
+    // PSVO_TIME_INTERP_FWD region.  PSVO_PATH_INTERP_PASS and width 256 keep
+    // the pass.
+    const bool fused = d->width == 128 && !(e->paths & PSVO_PATH_INTERP_PASS);
+    if (!fused) {
+        mark(e, st, PSVO_TIME_INTERP_FWD, 0);
+        ENG_CALL(psvo::interp_fwd_dev(st, m_early, m_dev, d->voxel_size, leaf_q, t_q, ray_of_q, rank_ray, c.rays_o,
+                                      c.rays_d, d->centres, d->vertex_idx, d->emb, ef.feat));
+        mark(e, st, PSVO_TIME_INTERP_FWD, 1);
+    }
     mark(e, st, PSVO_TIME_MLP_FWD, 0);  // stays open: host_forward or, sparse, step_select closes it
     if (im.on_aux) ENG_CALL(st_wait(st, e->prep_done, c.who));
-    const psvo::H2Rows h2o{ef.h2, nullptr, nullptr};
-    ENG_CALL(mlp_fwd_prepared(st, m_early, d->width, ef.feat, im.buf, ef.sdf, nullptr, nullptr, nullptr, m_dev, &h2o));
+    if (fused) {
+        const psvo::InterpSrc ip{leaf_q, ray_of_q, rank_ray, d->vertex_idx, t_q, c.rays_o, c.rays_d, d->centres,
+                                 reinterpret_cast<const float4 *>(d->emb), d->voxel_size};
+        ENG_CALL(psvo::mlp_trunk_interp(st, m_early, m_dev, ip, im.buf, ef.sdf, ef.h2, ef.feat));
+    } else {
+        const psvo::H2Rows h2o{ef.h2, nullptr, nullptr};
+        ENG_CALL(mlp_fwd_prepared(st, m_early, d->width, ef.feat, im.buf, ef.sdf, nullptr, nullptr, nullptr, m_dev,
+                                  &h2o));
+    }
     // the loss normalisers need only z (the sampler's rows): aux may start
     // them after these (a marker in front of them delays the interpolation)
     if (engine_overlap(e) && c.need_z_event) {
@@ -293,7 +311,8 @@ int host_forward(const MapRender &c, const Images &im, const EarlyFwd &ef, Rende
     // ---- forward: interpolation, decoder (after the previous step's
     // optimiser step when its tail ran on aux)
     ENG_CALL(join_adam(e, st, who));
-    if (!early_done) {  // (a batch beyond the device-sized forward's capacity: its region is already marked)
+    if (!early_done) {  // (a batch beyond the device-sized forward's capacity: no region of its own — the
+                        // device-sized forward marked it, or interpolated inside the trunk's region)
         if (!ef.on) mark(e, st, PSVO_TIME_INTERP_FWD, 0);
         ENG_CALL(psvo_interp_fwd(st, M, 16, d->voxel_size, o.s.leaf, o.s.tt, o.s.ray_of, o.rank_ray, c.rays_o, c.rays_d,
                                  d->centres, d->vertex_idx, d->emb, feat));

@@ -848,12 +848,16 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_fwd2(int64_t m, const flo
 // k_mlp_fwd2's first two layers, so the sdf is bit-identical to its output.
 constexpr int kLdsSdf2 = (kF2Buf0 + 16384) * 4;
 
-// IP: as k_mlp_fwd2's — the frame renderer's trunk pass
-template <bool IP = false>
-__global__ __launch_bounds__(kF2Threads, 1) void k_mlp_sdf2(int64_t m_host, const float *__restrict__ feat,
+// IP: as k_mlp_fwd2's — the frame renderer's trunk pass.  FS (with IP: the
+// mapping engine's device-sized trunk): `feat` is written, not read — the
+// interpolated rows, k_interp_fwd's table, for the kernels after the selection
+template <bool IP = false, bool FS = false>
+__global__ __launch_bounds__(kF2Threads, 1) void k_mlp_sdf2(int64_t m_host,
+                                                            std::conditional_t<FS, float, const float> *__restrict__ feat,
                                                             const float *__restrict__ img,
                                                             float *__restrict__ sdf_out, const int *__restrict__ m_dev,
                                                             float *__restrict__ h2_out, InterpSrc ip) {
+    static_assert(IP || !FS, "the feature rows are stored by the interpolating operand load");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     // m_dev: the count on the device, m_host the buffers' capacity (a larger
     // batch: nothing here, the host-sized launch after the read-back)
@@ -870,7 +874,9 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_sdf2(int64_t m_host, cons
     float xn[8];
     {
         const int64_t s = (u0 + wave) * kTileS + (lane & 31);
-        if constexpr (IP)
+        if constexpr (FS)
+            iload::load_x_interp<true>(ip, s, u0 + wave < u1 && s < m, h, xn, feat);
+        else if constexpr (IP)
             iload::load_x_interp(ip, s, u0 + wave < u1 && s < m, h, xn);
         else
             load_x(feat, s, u0 + wave < u1 && s < m, h, xn);
@@ -888,7 +894,9 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_sdf2(int64_t m_host, cons
         for (int i = 0; i < 8; ++i) x[i] = xn[i];
         if (u + kF2Waves < u1) {
             const int64_t sn = (u + kF2Waves) * kTileS + (lane & 31);
-            if constexpr (IP)
+            if constexpr (FS)
+                iload::load_x_interp<true>(ip, sn, sn < m, h, xn, feat);
+            else if constexpr (IP)
                 iload::load_x_interp(ip, sn, sn < m, h, xn);
             else
                 load_x(feat, sn, sn < m, h, xn);
@@ -2183,7 +2191,57 @@ int mlp_fwd_interp(hipStream_t st, int64_t m_cap, const int *m_dev, const Interp
                      rgb, nullptr, nullptr, m_dev, nullptr, nullptr, ip);
     return check_launch("mlp_fwd_interp");
 }
+// The mapping engine's device-sized sdf trunk (engine_step.cpp
+// device_forward): interp_fwd_dev + the plain trunk in one launch — the same
+// sdf, h2 rows and feature rows, bit for bit; rows >= m_dev[0], and every row
+// when m_dev[0] > m_cap, are left as they were.
+int mlp_trunk_interp(hipStream_t st, int64_t m_cap, const int *m_dev, const InterpSrc &ip, const float *images,
+                     float *sdf, float *h2_out, float *feat_out) {
+    PSVO_REQUIRE(m_cap >= 0 && m_dev && images && sdf && h2_out && feat_out && ip.leaf && ip.t && ip.ray_of &&
+                     ip.ray_index && ip.voxel_size > 0.f,
+                 "mlp_trunk_interp: bad arguments");
+    PSVO_REQUIRE(m_cap <= kMaxSamples, "mlp_trunk_interp: m_cap = %lld > %lld", (long long)m_cap,
+                 (long long)kMaxSamples);
+    if (m_cap == 0) return PSVO_OK;
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_mlp_sdf2<true, true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kLdsSdf2);
+        attr = true;
+    }
+    const int64_t tiles = div_up(m_cap, kF2Tile);
+    const int grid = (int)(tiles < device_cus() ? tiles : device_cus());
+    psvo::launch(k_mlp_sdf2<true, true>, dim3(grid), dim3(kF2Threads), kLdsSdf2, st, m_cap, feat_out, images, sdf,
+                 m_dev, h2_out, ip);
+    return check_launch("mlp_trunk_interp");
+}
 }  // namespace psvo
+
+// tests only: the device-sized trunk on its own — fused = 1 the engine's one
+// launch, fused = 0 the two kernels it replaces, into the same outputs
+extern "C" int psvo_debug_trunk_interp(void *stream, int fused, int64_t m_cap, const int *m_dev, const int *leaf,
+                                       const float *t, const int *ray_of, const int *ray_index, const float *rays_o,
+                                       const float *rays_d, const float *centres, const int *vertex_idx,
+                                       const float *emb, float voxel_size, const float *w1, const float *b1,
+                                       const float *w2, const float *b2, const float *w3, const float *b3,
+                                       const float *w4, const float *b4, const float *w5, const float *b5,
+                                       float *images, float *sdf, float *h2, float *feat) {
+    PSVO_REQUIRE(m_dev && images && sdf && h2 && feat, "debug_trunk_interp: null argument");
+    hipStream_t st = as_stream(stream);
+    const float *const dec[10] = {w1, b1, w2, b2, w3, b3, w4, b4, w5, b5};
+    int rc = psvo::mlp_images(stream, kW, dec, images);
+    if (rc) return rc;
+    if (fused) {
+        const InterpSrc ip{leaf, ray_of, ray_index, vertex_idx, t, rays_o, rays_d, centres,
+                           reinterpret_cast<const float4 *>(emb), voxel_size};
+        return psvo::mlp_trunk_interp(st, m_cap, m_dev, ip, images, sdf, h2, feat);
+    }
+    rc = psvo::interp_fwd_dev(st, m_cap, m_dev, voxel_size, leaf, t, ray_of, ray_index, rays_o, rays_d, centres,
+                              vertex_idx, emb, feat);
+    if (rc) return rc;
+    const H2Rows h2o{h2, nullptr, nullptr};
+    return psvo::mlp_fwd_prepared(stream, m_cap, kW, feat, images, sdf, nullptr, nullptr, nullptr, m_dev, &h2o);
+}
 
 extern "C" int psvo_mlp_fwd(void *stream, int64_t m, int width, const float *feat, const float *w1, const float *b1,
                             const float *w2, const float *b2, const float *w3, const float *b3, const float *w4,

@@ -88,6 +88,7 @@ _SIGNATURES = {
     "psvo_debug_select_samples": (_i32, [_vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _i32] + [_vp] * 7
                                   + [_i64, _i32] + [_vp] * 11 + [ctypes.c_uint32, _vp]),
     "psvo_debug_select_granules": (_i64, [_i64]),
+    "psvo_debug_trunk_interp": (_i32, [_vp, _i32, _i64] + [_vp] * 10 + [_f32] + [_vp] * 14),
     "psvo_debug_composite_loss": (_i32, [_vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _i32] + [_vp] * 11
                                   + [_i32, _vp]),
     "psvo_engine_queued": (_i32, [_vp]),

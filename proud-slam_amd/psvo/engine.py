@@ -378,15 +378,16 @@ class MappingEngine:
         L.call("psvo_map_adam_ex", self.handle, L.stream_of(self.emb.device), ctypes.addressof(self.desc),
                self.step_no, 1 if marked else 0)
 
-    PATH_QUERY_SPLIT, PATH_PADDED, PATH_DENSE_DECODER = 1, 2, 4
+    PATH_QUERY_SPLIT, PATH_PADDED, PATH_DENSE_DECODER, PATH_INTERP_PASS = 1, 2, 4, 8
 
     def set_paths(self, paths):
         """Run the alternative production kernels on this single-GPU engine
         (cross-checks): PATH_QUERY_SPLIT — the query's statistics / rank pass
         and sample scan as kernels of their own; PATH_PADDED — the padded z
         copy and in-step loss normalisers; PATH_DENSE_DECODER — the width-128
-        decoder on every sample instead of the sparse decoder
-        (psvo_engine_set_paths)."""
+        decoder on every sample instead of the sparse decoder;
+        PATH_INTERP_PASS — the device-sized forward's interpolation as a pass
+        of its own instead of inside the sdf trunk (psvo_engine_set_paths)."""
         L.call("psvo_engine_set_paths", self.handle, int(paths))
 
     def select_stats(self, reset=False):
