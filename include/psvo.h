@@ -263,7 +263,7 @@ int psvo_composite_loss(void *stream, int64_t r_hit, int s_max, float truncation
  * images, rebuilt by every call; psvo_mlp_bwd reuses them (same weights).
  * Training mode: masks u64[M][2][3] (ReLU masks, needed by any psvo_mlp_bwd)
  * and act f32[4][ceil(M/64)*64*128] (h1, h2, f, c1 in 32-sample CF tiles, see
- * mlp.hip; needed only for weight gradients) are written when non-NULL;
+ * mlp128.h; needed only for weight gradients) are written when non-NULL;
  * act requires masks.  Inference: both NULL; rgb NULL as well: the sdf
  * alone (Decoder.get_sdf, mesh lattices — h1, h2 and W3's sdf row only).
  * Width 256 (W1[256,16], W2[256,256], W3[129,256], W4[256,144], W5[3,256];
@@ -273,7 +273,7 @@ int psvo_composite_loss(void *stream, int64_t r_hit, int s_max, float truncation
 int64_t psvo_mlp_image_floats(void);
 /* width-aware sizes (width 128 or 256; -1 otherwise): operand images, the
  * training forward's activations (act) and ReLU masks (u64 words), the
- * backward's workspace */
+ * backward's workspace (n_split: accepted for compatibility and ignored) */
 int64_t psvo_mlp_image_floats_w(int width);
 int64_t psvo_mlp_act_floats(int64_t m, int width);
 int64_t psvo_mlp_mask_words(int64_t m, int width);
@@ -283,13 +283,17 @@ int psvo_mlp_fwd(void *stream, int64_t m, int width, const float *feat, const fl
                  const float *b4, const float *w5, const float *b5, float *images, float *sdf, float *rgb,
                  float *act, uint64_t *masks);
 
-/* Floats of device workspace psvo_mlp_bwd needs for m samples. */
+/* Floats of device workspace psvo_mlp_bwd needs for m samples (width 128).
+ * n_split is accepted for compatibility and ignored: the backward writes one
+ * weight-gradient slab per workgroup, one workgroup per CU. */
 int64_t psvo_mlp_workspace_floats(int64_t m, int n_split);
 
 /* Backward given g_sdf[M], g_rgb[M,3] and the training forward's rgb / act /
  * masks: writes dfeat[M,16] and the 10 parameter gradients (overwrite, or
- * add when `accumulate`); split-K over ~n_split sample ranges with a
- * deterministic slab reduction.  gw1 == NULL (frozen decoder, e.g.
+ * add when `accumulate`): every workgroup of the backward sums its own
+ * sample range into one slab per weight matrix, and the slabs are added in
+ * a fixed order (deterministic).  n_split (> 0) is accepted for
+ * compatibility and ignored.  gw1 == NULL (frozen decoder, e.g.
  * tracking): dfeat only — act may then be NULL and the other gradient
  * pointers are ignored. */
 int psvo_mlp_bwd(void *stream, int64_t m, int width, const float *feat, const float *w1, const float *b1,

@@ -145,7 +145,8 @@ struct psvo_engine {
     hipStream_t q2s = nullptr;      // data parallel: the queries' second halves (QuerySet::p2_pending)
     hipEvent_t in_ready = nullptr;  // the caller's stream position at psvo_map_query
     // the embedding backward runs on `aux` beside the decoder's weight
-    // gradients (k_interp_bwd's 8-KB workgroups fit next to k_mlp_dw2's 152 KB)
+    // gradients where the decoder's backward does not run it itself (width
+    // 256: k_interp_bwd's 8-KB workgroups fit next to k_dec256_dw's 104 KB)
     // (and the loss normalisers beside the decoder forward; data parallel,
     // also the loss value beside the decoder backward)
     hipStream_t aux = nullptr;

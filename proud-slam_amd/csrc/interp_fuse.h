@@ -1,6 +1,6 @@
 // The interpolation backward (interp.hip's k_interp_bwd arithmetic) of one
 // 16-sample unit on a decoder δ-chain wave, shared by the fused width-128
-// (mlp.hip k_mlp_bwd3) and width-256 (mlp256.hip k_dec256_bwd) backwards:
+// (mlp_bwd.hip k_mlp_bwd3, k_mlp_trunk_fb) and width-256 (mlp256.hip k_dec256_bwd) backwards:
 // lane (n, q) holds sample n's dfeat dims 4q..4q+3 in both chains.
 #pragma once
 

@@ -1,5 +1,5 @@
 // The interpolation forward (interp.hip's k_interp_fwd arithmetic) as the
-// operand load of the width-128 decoder's forward kernels (mlp.hip k_mlp_sdf2
+// operand load of the width-128 decoder's forward kernels (mlp_fwd.hip k_mlp_sdf2
 // / k_mlp_fwd2, the frame renderer's instantiations): a sample's 16 features
 // are formed in registers from (leaf, t, ray) and the embedding rows and go
 // straight into the W1 MFMAs — no [M,16] feature rows read back from HBM (the
@@ -21,11 +21,11 @@ struct InterpSrc {
     float voxel_size;
 };
 
-// mlp.hip: the sdf trunk (rgb null) or the whole width-128 forward on the
+// mlp_fwd.hip: the sdf trunk (rgb null) or the whole width-128 forward on the
 // m_dev[0] <= m_cap samples of `ip`; m_cap only sizes the grid
 int mlp_fwd_interp(hipStream_t st, int64_t m_cap, const int *m_dev, const InterpSrc &ip, const float *images,
                    float *sdf, float *rgb);
-// mlp.hip: the mapping engine's device-sized sdf trunk — as mlp_fwd_interp's,
+// mlp_fwd.hip: the mapping engine's device-sized sdf trunk — as mlp_fwd_interp's,
 // and it leaves what interp_fwd_dev + the plain trunk leave: every sample's
 // h2 row (h2_out [m_cap][128]) and feature row (feat_out [m_cap][16]).
 // m_dev[0] > m_cap: nothing is written
@@ -75,7 +75,7 @@ namespace iload {
     }
 
 // Lane (n = lane & 31, h = lane >> 5) of a 32-sample unit gets x[t] = feature
-// 2t + h of sample s (mlp.hip load_x's layout).  The lane forms features
+// 2t + h of sample s (mlp128.h load_x's layout).  The lane forms features
 // 8h .. 8h + 7 itself — two 16-B loads per embedding row, the wave reads whole
 // 64-B rows — and the two lanes of a sample swap the halves the other one
 // needs.  All 64 lanes must call it (the swap is a cross-lane read); !valid:

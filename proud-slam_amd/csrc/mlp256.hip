@@ -178,14 +178,6 @@ __global__ __launch_bounds__(256) void k_dec256_prep(Params p, float *__restrict
 __device__ __forceinline__ uint32_t lds_addr(const float *l) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) float *)l;
 }
-// global → LDS 16 B per lane (LDS destination = wave-uniform base + lane x 16)
-__device__ __forceinline__ void glds16(const float *g, float *l) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(g), "s"(__builtin_amdgcn_readfirstlane(lds_addr(l)))
-                 : "memory");
-}
 // s_waitcnt vmcnt(N) lgkmcnt(0) (expcnt untouched); N < 64
 template <int N>
 __device__ __forceinline__ void wait_vm_lds() {
@@ -201,7 +193,8 @@ __device__ __forceinline__ void chunk_barrier() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
-// the same with a uniform (SGPR) base and a 32-bit per-lane byte offset
+// global → LDS 16 B per lane (LDS destination = wave-uniform base + lane x 16),
+// from a uniform (SGPR) base and a 32-bit per-lane byte offset
 __device__ __forceinline__ void glds16s(const float *base, uint32_t voff, float *l) {
     uint32_t keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
@@ -295,7 +288,7 @@ __device__ __forceinline__ void zero(f32x4 (&acc)[kNC][NOB]) {
         for (int ob = 0; ob < NOB; ++ob) acc[c][ob] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 // ReLU in place; mask bit 4 ob + i = (value > 0), one word per sample group.
-// No compares (mlp.hip's relu): y = max(v, 0) and (−u) & ~u (u = bits of y)
+// No compares (mlp128_chain32.h's relu): y = max(v, 0) and (−u) & ~u (u = bits of y)
 // has its sign bit set exactly for positive non-zero y — per-element compare
 // results held as SGPR-pair lane masks spilled ~730 SGPRs to VGPR lanes here
 // (v_writelane / v_readlane in the tile loop).
@@ -1008,17 +1001,6 @@ __global__ __launch_bounds__(256) void k_dec256_dw_reduce(DwPlan pl, const float
 }  // namespace
 
 // ---- host side -----------------------------------------------------------------
-static int device_cus256() {
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-            cus = 256;
-    }
-    return cus;
-}
-
 int64_t dec256_tiles16(int64_t m) { return (m + kTileWG - 1) / kTileWG * kWaves; }
 int64_t dec256_image_floats() { return kImgTotal; }
 int64_t dec256_act_floats(int64_t m) { return dec256_tiles16(m) * 16 * (256 + 256 + 144 + 256); }
@@ -1032,7 +1014,7 @@ static void dw_plan(int64_t m, DwPlan *pl, int64_t *slab_floats) {
     // of HBM (≈20 GB/s)) — L2: 131 kFLOP | 2,048 B, L3 / L4: 73.7 kFLOP |
     // 1,600 B, L1 + L5: 16.4 kFLOP | 2,112 B (memory-bound: by FLOPs alone it
     // got 14 workgroups and set the kernel's time)
-    const int cus = device_cus256();
+    const int cus = device_cus();
     // per-type weights measured at config C (466 k samples, one box, decoder
     // alone): {213,120,120,107} 1,310 us -> {213,130,130,60} 1,195-1,200 us —
     // the W1 / W5 type's byte-bound tiles finish early with fewer workgroups
@@ -1086,24 +1068,22 @@ int dec256_images(hipStream_t st, const float *const *dec, float *images) {
     return check_launch("dec256_images");
 }
 
-static int grid_for(int64_t n_tiles) {
-    const int cus = device_cus256();
-    return (int)(n_tiles < cus ? n_tiles : cus);
-}
-
-int dec256_fwd(hipStream_t st, int64_t m, const float *feat, const float *images, float *sdf, float *rgb, float *act,
-               uint64_t *masks, const int *m_dev) {
+int dec256_fwd(hipStream_t st, int64_t m, const float *feat, const float *const *dec, float *images, float *sdf,
+               float *rgb, float *act, uint64_t *masks, const int *m_dev) {
+    PSVO_REQUIRE(m >= 0, "mlp_fwd: m < 0");
+    PSVO_REQUIRE(images != nullptr, "mlp_fwd: images workspace required (psvo_mlp_image_floats_w floats)");
+    PSVO_REQUIRE(act == nullptr || masks != nullptr, "mlp_fwd: act needs masks");
+    PSVO_REQUIRE(m <= ((int64_t)1 << 31) / 256, "mlp_fwd: m = %lld too large", (long long)m);
+    if (dec) {
+        const int rc = dec256_images(st, dec, images);
+        if (rc) return rc;
+    }
     if (m == 0) return PSVO_OK;
     const int64_t n_tiles = (m + kChainTile - 1) / kChainTile;
+    const dim3 grid(persistent_grid(n_tiles)), block(kCThreads);
+    const int lds = (((kVecN + 63) / 64) * 64 + kRing * kChunkFloats) * 4;
     if (!rgb && !act && !masks) {  // sdf only: the trunk
-        const int lds = (((kVecN + 63) / 64) * 64 + kRing * kChunkFloats) * 4;
-        static bool tattr = false;
-        if (!tattr) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec256_trunk),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            tattr = true;
-        }
-        psvo::launch(k_dec256_trunk, dim3(grid_for(n_tiles)), dim3(kCThreads), lds, st, m, feat, images, sdf, m_dev);
+        launch_lds<k_dec256_trunk>(grid, block, lds, st, m, feat, images, sdf, m_dev);
         return check_launch("dec256_trunk");
     }
     const int64_t n16 = dec256_tiles16(m);
@@ -1115,15 +1095,7 @@ int dec256_fwd(hipStream_t st, int64_t m, const float *feat, const float *images
         a.c1 = a.fx + n16 * 144 * 16;
     }
     a.masks = masks;
-    const int lds = (((kVecN + 63) / 64) * 64 + kRing * kChunkFloats) * 4;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec256_fwd),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr = true;
-    }
-    psvo::launch(k_dec256_fwd, dim3(grid_for(n_tiles)), dim3(kCThreads), lds, st, m, n_tiles, feat, images, sdf,
-                 rgb, a, m_dev);
+    launch_lds<k_dec256_fwd>(grid, block, lds, st, m, n_tiles, feat, images, sdf, rgb, a, m_dev);
     return check_launch("dec256_fwd");
 }
 
@@ -1131,6 +1103,9 @@ int dec256_bwd(hipStream_t st, int64_t m, const float *feat, const float *images
                const uint64_t *masks, const float *g_sdf, const float *g_rgb, float *dfeat, float *const gw[5],
                float *const gb[5], int accumulate, float *workspace, hipEvent_t dfeat_ready,
                const InterpFuse *ip, const int *m_dev) {
+    PSVO_REQUIRE(m >= 0, "mlp_bwd: bad sizes");
+    PSVO_REQUIRE(images != nullptr && masks != nullptr, "mlp_bwd: images / masks of the training forward required");
+    PSVO_REQUIRE(gw[0] == nullptr || act != nullptr, "mlp_bwd: weight gradients need the forward's activations");
     PSVO_REQUIRE(ip == nullptr || (kNC == 1 && gw[0] != nullptr),
                  "dec256_bwd: the fused interpolation backward needs the weight-gradient path (1 group per wave)");
     (void)feat;
@@ -1157,12 +1132,6 @@ int dec256_bwd(hipStream_t st, int64_t m, const float *feat, const float *images
     bool bound = false;
     if (m > 0) {
         const int lds = (kRing * kChunkFloats + kCWaves * 512) * 4;  // ring + per-wave scatter staging
-        static bool attr = false;
-        if (!attr) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec256_bwd),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            attr = true;
-        }
         // dfeat_ready through the dispatch's stop event (no marker packet
         // between the backward and the weight-gradient kernel on st)
         static const bool bind_env = [] {
@@ -1170,8 +1139,8 @@ int dec256_bwd(hipStream_t st, int64_t m, const float *feat, const float *images
             return !(v && v[0] == '0');
         }();
         psvo::StopBind sb(bind_env ? dfeat_ready : nullptr);
-        psvo::launch(k_dec256_bwd, dim3(grid_for(n_tiles)), dim3(kCThreads), lds, st, m, n_tiles, images, rgb,
-                     g_sdf, g_rgb, a, d, dfeat, ip ? *ip : InterpFuse{}, m_dev);
+        launch_lds<k_dec256_bwd>(dim3(persistent_grid(n_tiles)), dim3(kCThreads), lds, st, m, n_tiles, images, rgb,
+                                 g_sdf, g_rgb, a, d, dfeat, ip ? *ip : InterpFuse{}, m_dev);
         bound = sb.consumed();
         const int rc = check_launch("dec256_bwd");
         if (rc) return rc;
@@ -1190,14 +1159,8 @@ int dec256_bwd(hipStream_t st, int64_t m, const float *feat, const float *images
     op.a[3] = d.d1; op.b[3] = a.fx;   // L1 (x rows of fx)
     op.a5 = d.d5; op.b5 = a.c1;       // L5
     for (int t = 0; t < 4; ++t) op.fa[t] = op.fb[t] = 0;
-    static bool dattr = false;
-    if (!dattr) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec256_dw),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kDwLds);
-        dattr = true;
-    }
     if (m > 0) {
-        psvo::launch(k_dec256_dw, dim3(pl.wg_begin[4]), dim3(kThreads), kDwLds, st, op, pl, slabs, m_dev);
+        launch_lds<k_dec256_dw>(dim3(pl.wg_begin[4]), dim3(kThreads), kDwLds, st, op, pl, slabs, m_dev);
         const int rc = check_launch("dec256_dw");
         if (rc) return rc;
     } else if (hipMemsetAsync(slabs, 0, slab_floats * sizeof(float), st) != hipSuccess) {

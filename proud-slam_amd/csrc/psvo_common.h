@@ -362,6 +362,23 @@ int64_t select_granules(int64_t r_hit);
 int compact_rays(hipStream_t st, int64_t r_hit, int cap, const int *s_idx, const float *s_depth, const int *offsets,
                  int *leaf, float *t, int *ray_of_sample);
 
+// ---- the decoder's host glue (decoder.cpp) ----------------------------------
+// the device's CU count (256 when it cannot be read); a persistent kernel's grid: min(units, CUs)
+int device_cus();
+inline int persistent_grid(int64_t units) {
+    const int cus = device_cus();
+    return (int)(units < cus ? units : cus);
+}
+// psvo::launch of a kernel with `lds` bytes of dynamic LDS, allowed once per
+// kernel (the flag is per instantiation of this template, i.e. per kernel
+// address: k_x<true> and k_x<false> each get theirs)
+template <auto Kernel, typename... A>
+inline void launch_lds(dim3 grid, dim3 block, int lds, hipStream_t st, A &&...a) {
+    [[maybe_unused]] static const hipError_t allowed = hipFuncSetAttribute(
+        reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    launch(Kernel, grid, block, (uint32_t)lds, st, static_cast<A &&>(a)...);
+}
+
 // width-256 decoder (mlp256.hip): sizes, operand images, forward (act /
 // masks NULL: inference), backward (gw[0] NULL: δ chain to dfeat only)
 int64_t dec256_tiles16(int64_t m);
@@ -371,10 +388,11 @@ int64_t dec256_mask_words(int64_t m);
 int64_t dec256_workspace_floats(int64_t m);
 // dec: the ten parameter tensors W1, b1, ..., W5, b5 (psvo_map_desc::dec)
 int dec256_images(hipStream_t st, const float *const *dec, float *images);
+// dec (or null: `images` already holds them): the images are built first.
 // rgb, act and masks all null: the sdf trunk only (k_dec256_trunk, the same sdf
 // bits).  m_dev: the sample count read on the device (<= m; buffers sized for m)
-int dec256_fwd(hipStream_t st, int64_t m, const float *feat, const float *images, float *sdf, float *rgb, float *act,
-               uint64_t *masks, const int *m_dev = nullptr);
+int dec256_fwd(hipStream_t st, int64_t m, const float *feat, const float *const *dec, float *images, float *sdf,
+               float *rgb, float *act, uint64_t *masks, const int *m_dev = nullptr);
 struct InterpFuse;
 // ip (the mapping engine's width-256 step): the interpolation backward runs
 // inside the δ-chain kernel (dfeat is then not stored), as at width 128
@@ -382,6 +400,27 @@ int dec256_bwd(hipStream_t st, int64_t m, const float *feat, const float *images
                const uint64_t *masks, const float *g_sdf, const float *g_rgb, float *dfeat, float *const gw[5],
                float *const gb[5], int accumulate, float *workspace, hipEvent_t dfeat_ready,
                const InterpFuse *ip = nullptr, const int *m_dev = nullptr);
+
+// width-128 decoder (mlp_fwd.hip; dec128_workspace_floats and dec128_bwd:
+// mlp_bwd.hip), the same interface plus the sparse decoder's arguments;
+// mlp_fwd_interp / mlp_trunk_interp (interp_load.h) are its forwards that
+// interpolate their own features
+struct H2Rows;
+struct TrunkBwd;
+int64_t dec128_image_floats();
+int64_t dec128_act_floats(int64_t m);
+int64_t dec128_mask_words(int64_t m);
+int64_t dec128_workspace_floats(int64_t m);
+int dec128_images(hipStream_t st, const float *const *dec, float *images);
+// rgb null: the sdf only (k_mlp_sdf2, the same sdf bits; inference).  h2: H2Rows below
+int dec128_fwd(hipStream_t st, int64_t m, const float *feat, const float *const *dec, float *images, float *sdf,
+               float *rgb, float *act, uint64_t *masks, const int *m_dev, const H2Rows *h2);
+// the arguments of mlp_bwd below
+int dec128_bwd(hipStream_t st, int64_t m, const float *feat, const float *images, const float *rgb, const float *act,
+               const uint64_t *masks, const float *g_sdf, const float *g_rgb, float *dfeat, float *const gw[5],
+               float *const gb[5], int accumulate, int n_split, float *workspace, hipEvent_t dfeat_ready,
+               const InterpFuse *ip, hipStream_t reduce_stream, const int *m_dev, const TrunkBwd *tb,
+               const int *x_src);
 
 constexpr int kXchMaxFrames = 64;  // keyframes per psvo_map_step_frames call
 

@@ -412,7 +412,7 @@ extern "C" int psvo_render_frame(psvo_engine *e, void *stream, const psvo_map_de
         } else {
             R_CALL(interp_fwd_dev(st, slots, m_dev, d->voxel_size, leaf, tt, ray_of, ray_index, rays_o, rays_d,
                                   d->centres, d->vertex_idx, d->emb, feat));
-            R_CALL(dec256_fwd(st, slots, feat, images, sdf, nullptr, nullptr, nullptr, m_dev));
+            R_CALL(dec256_fwd(st, slots, feat, nullptr, images, sdf, nullptr, nullptr, nullptr, m_dev));
         }
         const dim3 rg(div_up(n, kSelWavesR)), rb(64 * kSelWavesR);
         psvo::launch(k_render_select_count, rg, rb, 0, st, (int)n, tr, offsets, tt, sdf, frame, zmin_t, nc);
@@ -429,7 +429,7 @@ extern "C" int psvo_render_frame(psvo_engine *e, void *stream, const psvo_map_de
         } else {
             R_CALL(interp_fwd_dev(st, slots, mc_dev, d->voxel_size, leaf_c, t_c, ray_c, ray_index, rays_o, rays_d,
                                   d->centres, d->vertex_idx, d->emb, feat));
-            R_CALL(dec256_fwd(st, slots, feat, images, sdf_c, rgb_c, nullptr, nullptr, mc_dev));
+            R_CALL(dec256_fwd(st, slots, feat, nullptr, images, sdf_c, rgb_c, nullptr, nullptr, mc_dev));
         }
         psvo::launch(k_render_composite, rg, rb, 0, st, (int)n, tr, offsets, offc, tt, sdf, rgb_c, zmin_t, ray_index,
                      color, depth, z_min, mask);

@@ -6,7 +6,7 @@ embedder 'none', skips []:
   rgb = σ(L5(ReLU(L4([f, x]))))
 
 On a GPU forward() runs the fused fp32-MFMA kernels of libpsvo through
-DecoderMLP: width 128 (every Replica config, csrc/mlp.hip) and width 256
+DecoderMLP: width 128 (every Replica config, csrc/mlp_fwd.hip, mlp_bwd.hip) and width 256
 (ScanNet / ARKit, configs/scannet/scannet.yaml:17, csrc/mlp256.hip).
 get_values() (mesh extraction, no grad) uses the PyTorch layers.
 """
@@ -59,7 +59,7 @@ class DecoderMLP(Function):
         dev = feat.device
         g_sdf = torch.zeros((m,), device=dev) if g_sdf is None else g_sdf.contiguous().float()
         g_rgb = torch.zeros((m, 3), device=dev) if g_rgb is None else g_rgb.contiguous().float()
-        n_split = 256  # split-K workgroups of the weight gradients (one per CU)
+        n_split = 256  # accepted for compatibility and ignored: one weight-gradient slab per workgroup
         ws = torch.empty((int(L.lib().psvo_mlp_workspace_floats_w(m, ctx.width, n_split)),), dtype=torch.float32,
                          device=dev)
         dfeat = torch.empty((m, 16), dtype=torch.float32, device=dev)

@@ -4,7 +4,7 @@ backward on the aux stream, overlapping the decoder kernels) vs 'timed'
 steps (the HIP-event breakdown run: every launch on one stream, so each
 kernel's duration is its own).  The roofline numbers in bench.py come from
 the timed steps; a plain --stats average mixes both modes (k_interp_bwd
-co-resident with k_mlp_dw2 runs longer, by design)."""
+co-resident with the width-256 decoder's k_dec256_dw runs longer, by design)."""
 import collections
 import csv
 import json
