@@ -593,8 +593,20 @@ int psvo_map_discard(psvo_engine *e);
  * of its own (k_interp_fwd, then the sdf trunk reading the feature rows: the
  * host-sized and width-256 form) instead of inside the width-128 trunk's
  * operand load.  An engine is created with this bit set when the environment
- * has PSVO_INTERP_PASS=1 (an A/B of the two schedules from one binary). */
-enum { PSVO_PATH_QUERY_SPLIT = 1, PSVO_PATH_PADDED = 2, PSVO_PATH_DENSE_DECODER = 4, PSVO_PATH_INTERP_PASS = 8 };
+ * has PSVO_INTERP_PASS=1 (an A/B of the two schedules from one binary);
+ * PSVO_PATH_BWD_TWO_LAUNCH — the sparse decoder's backward as two launches,
+ * the loss-only samples' trunk kernel (k_mlp_trunk_fb) after the composited
+ * samples' k_mlp_bwd3, each over the whole grid with slabs of its own,
+ * instead of one launch whose workgroups are divided between the two classes
+ * (the same sums in another order).  Set at creation when the environment has
+ * PSVO_BWD_TWO_LAUNCH=1. */
+enum {
+    PSVO_PATH_QUERY_SPLIT = 1,
+    PSVO_PATH_PADDED = 2,
+    PSVO_PATH_DENSE_DECODER = 4,
+    PSVO_PATH_INTERP_PASS = 8,
+    PSVO_PATH_BWD_TWO_LAUNCH = 16
+};
 int psvo_engine_set_paths(psvo_engine *e, int paths);   /* with no query queued */
 
 /* The sparse decoder's sample selection (synchronises `stream`, which must
@@ -620,6 +632,16 @@ int psvo_engine_gate_stream(psvo_engine *e, void *stream);
  * (the path a workgroup kept off the CUs by other work takes).  mask 0: the
  * defaults.  Process-wide; takes effect at the next launch. */
 int psvo_debug_set_lookback(int mask, int spin_bound, int delay_us);
+/* Balance sweeps and tests: the cost model by which the one-launch decoder
+ * backward divides its workgroups between the two sample classes — the
+ * per-round costs of the composited class (cost_a) and the loss-only class
+ * (cost_b) and the latter's cost before its first round (cost_b0), in any
+ * common unit, 1..4096 (cost_b0 from 0); all 0: the built-in constants.
+ * Process-wide; takes effect at the next launch.  psvo_debug_bwd_split: the
+ * composited class's workgroups of n_wg for units_a / units_b 16-sample units
+ * under the current model (-1: bad arguments). */
+int psvo_debug_set_bwd_split(int cost_a, int cost_b, int cost_b0);
+int psvo_debug_bwd_split(int64_t units_a, int64_t units_b, int n_wg);
 /* Tests only: look-back blocks helped so far ([0] traversal, [1] sampler,
  * [2] sample selection); reset != 0 zeroes them.  Synchronises the device. */
 int psvo_debug_lb_helps(int64_t *out3, int reset);

@@ -34,7 +34,31 @@ LbCtl lb_ctl(int site) {
     return LbCtl{on && g_lb_debug_bound >= 0 ? g_lb_debug_bound : kLbSpinMax, on ? g_lb_debug_delay : 0};
 }
 
+// the one-launch decoder backward's cost model (psvo_common.h bwd_split_na)
+static BwdSplitCost g_bwd_split_cost = kBwdSplitCost;
+BwdSplitCost bwd_split_cost() { return g_bwd_split_cost; }
+
 }  // namespace psvo
+
+// balance sweeps and tests: the cost model of the one-launch decoder backward
+// (per-round costs a, b of class A / class B and class B's pre-loop cost b0;
+// all 0: the built-in constants)
+extern "C" int psvo_debug_set_bwd_split(int cost_a, int cost_b, int cost_b0) {
+    if (cost_a == 0 && cost_b == 0 && cost_b0 == 0) {
+        psvo::g_bwd_split_cost = psvo::kBwdSplitCost;
+        return PSVO_OK;
+    }
+    PSVO_REQUIRE(cost_a >= 1 && cost_a <= 4096 && cost_b >= 1 && cost_b <= 4096 && cost_b0 >= 0 && cost_b0 <= 4096,
+                 "debug_set_bwd_split: bad arguments");
+    psvo::g_bwd_split_cost = psvo::BwdSplitCost{cost_a, cost_b, cost_b0};
+    return PSVO_OK;
+}
+
+// tests: class A's workgroups of n_wg under the current cost model (-1: bad arguments)
+extern "C" int psvo_debug_bwd_split(int64_t units_a, int64_t units_b, int n_wg) {
+    if (units_a < 0 || units_b < 0 || n_wg < 1) return -1;
+    return psvo::bwd_split_na(units_a, units_b, n_wg, psvo::bwd_split_cost());
+}
 
 extern "C" int psvo_debug_set_lookback(int mask, int spin_bound, int delay_us) {
     PSVO_REQUIRE(mask >= 0 && mask <= 7 && spin_bound >= -1 && delay_us >= 0 && delay_us <= 100000,

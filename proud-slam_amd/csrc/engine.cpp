@@ -281,6 +281,9 @@ extern "C" psvo_engine *psvo_engine_new(void) {
     // (psvo_engine_set_paths replaces the whole mask)
     const char *ipass = getenv("PSVO_INTERP_PASS");
     if (ipass && ipass[0] == '1') e->paths |= PSVO_PATH_INTERP_PASS;
+    // PSVO_BWD_TWO_LAUNCH=1: likewise the two-launch decoder backward
+    const char *two = getenv("PSVO_BWD_TWO_LAUNCH");
+    if (two && two[0] == '1') e->paths |= PSVO_PATH_BWD_TWO_LAUNCH;
     for (auto &q : e->qs)
         if (query_set_init(q) != PSVO_OK) {
             psvo_engine_free(e);
@@ -325,7 +328,7 @@ extern "C" int psvo_engine_set_exchange(psvo_engine *e, int rank, int world, int
 
 extern "C" int psvo_engine_set_paths(psvo_engine *e, int paths) {
     PSVO_REQUIRE(e && (paths & ~(PSVO_PATH_QUERY_SPLIT | PSVO_PATH_PADDED | PSVO_PATH_DENSE_DECODER |
-                               PSVO_PATH_INTERP_PASS)) == 0,
+                               PSVO_PATH_INTERP_PASS | PSVO_PATH_BWD_TWO_LAUNCH)) == 0,
                  "engine_set_paths: bad arguments");
     PSVO_REQUIRE(e->q_count == 0, "engine_set_paths: queries are queued");
     e->paths = paths;

@@ -777,7 +777,8 @@ int step_backward(MapStep &s) {
     const psvo::InterpFuse ipf_b{k.leaf + M, k.ray_of + M, q.rank_ray, d->vertex_idx, k.tt + M, s.rays_o, s.rays_d,
                                  d->centres, d->emb, d->voxel_size, grad_emb, gx ? gx + 3 * M : nullptr, s.mark_into};
     const psvo::TrunkBwd tbw{s.sel_cnt ? s.sel_cnt + 1 : nullptr, s.g_sdf_s + M, s.h2_src ? k.feat : k.feat + M * 16,
-                             fuse_ib ? &ipf_b : nullptr, s.h2_src ? q.h2 : nullptr, s.h2_src ? s.h2_src + M : nullptr};
+                             fuse_ib ? &ipf_b : nullptr, s.h2_src ? q.h2 : nullptr, s.h2_src ? s.h2_src + M : nullptr,
+                             (e->paths & PSVO_PATH_BWD_TWO_LAUNCH) != 0};
     // (split: the weight-gradient slab sum on aux, step_tail)
     ENG_CALL(mlp_bwd(st, M, d->width, k.feat, q.images, k.rgb_s, k.act, k.masks, s.g_sdf_s, s.g_rgb_s, dfeat, s.G, 0,
                      n_split, mlp_ws, s.overlap ? e->dfeat_ready : nullptr, fuse_ib ? &ipf : nullptr,

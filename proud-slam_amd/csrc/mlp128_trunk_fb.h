@@ -1,7 +1,9 @@
 // Width-128 decoder, the sparse decoder's class B (mlp128.h: the layer
 // equations and layouts): k_mlp_trunk_fb, the sdf trunk's forward and
-// backward in one kernel, and its launcher.  dec128_bwd (mlp_bwd.hip) queues
-// it after k_mlp_bwd3; k_mlp_dw_reduce adds its slabs to that kernel's.
+// backward in one kernel, and its launcher.  Its body also runs on the
+// class-B workgroups of mlp_bwd.hip's k_mlp_bwd3<W, H2> (the default); as a
+// launch of its own dec128_bwd queues it after k_mlp_bwd3<W>, and
+// k_mlp_dw_reduce adds its slabs to that kernel's.
 //
 // A header of mlp_bwd.hip, not a translation unit of its own: k_mlp_bwd3 and
 // this kernel share mlp128_chain16.h's helpers, and compiled apart both come
@@ -162,27 +164,27 @@ __device__ __forceinline__ void trunk_fwd_unit(float *lds, __amdgpu_buffer_rsrc_
     lds_u_store<8>(lds + kT4H2 + k * kUImg, wb, fb);
 }
 
+//
+// The body is a device function of its workgroup's place: workgroup `wg` of
+// the `n_wg` that share the m samples, writing slab `b` (k_mlp_trunk_fb below:
+// the whole grid; mlp_bwd.hip's k_mlp_bwd3<W, H2>: the grid's class-B part).
 template <bool H2>
-__global__ __launch_bounds__(kF2Threads, 1) void k_mlp_trunk_fb(const int *__restrict__ m_dev,
-                                                                const float *__restrict__ img,
-                                                                const float *__restrict__ g_sdf,
-                                                                const float *__restrict__ feat, DwGrid g,
-                                                                float *__restrict__ slabs, InterpFuse ip,
-                                                                const float *__restrict__ h2,
-                                                                const int *__restrict__ h2_src) {
+__device__ __forceinline__ void mlp_trunk_fb_body(const unsigned wg, const unsigned n_wg, const int b, const int64_t m,
+                                                  const float *__restrict__ img, const float *__restrict__ g_sdf,
+                                                  const float *__restrict__ feat, const DwGrid &g,
+                                                  float *__restrict__ slabs, const InterpFuse &ip,
+                                                  const float *__restrict__ h2, const int *__restrict__ h2_src) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int64_t m = __builtin_amdgcn_readfirstlane(*m_dev);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t n_units = (m + kU - 1) / kU;
-    const int64_t u0 = n_units * blockIdx.x / gridDim.x, u1 = n_units * (blockIdx.x + 1) / gridDim.x;
+    const int64_t u0 = n_units * wg / n_wg, u1 = n_units * (wg + 1) / n_wg;
     const int n_rounds = (int)((u1 - u0 + 3) / 4);
     float *const h2set = lds + kT4H2, *const h1set = lds + kT4H1, *const cf = lds + kT4CF;
     auto xset = [&](int par) { return lds + kT4X + (par & 1) * 4 * 16 * kU; };
     stage8(lds, img + kImgVec, kVecPad, wave, lane);
     wait_vm(0);
     raw_barrier();
-    const int b = blockIdx.x;
     const int i = lane & 31, h = lane >> 5;
     const int n = lane & 15, q = lane >> 4;
     const int sn = (n & 1) * 8 + (n >> 1);                     // the sample's slot in a unit image
@@ -403,6 +405,18 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_trunk_fb(const int *__res
             store_nt(s3, 129 * 128, v);
         }
     }
+}
+
+template <bool H2>
+__global__ __launch_bounds__(kF2Threads, 1) void k_mlp_trunk_fb(const int *__restrict__ m_dev,
+                                                                const float *__restrict__ img,
+                                                                const float *__restrict__ g_sdf,
+                                                                const float *__restrict__ feat, DwGrid g,
+                                                                float *__restrict__ slabs, InterpFuse ip,
+                                                                const float *__restrict__ h2,
+                                                                const int *__restrict__ h2_src) {
+    const int64_t m = __builtin_amdgcn_readfirstlane(*m_dev);
+    mlp_trunk_fb_body<H2>(blockIdx.x, gridDim.x, blockIdx.x, m, img, g_sdf, feat, g, slabs, ip, h2, h2_src);
 }
 
 // one slab of g's layout per workgroup (the caller binds the stop event and checks the launch)

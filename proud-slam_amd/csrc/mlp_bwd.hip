@@ -1,10 +1,13 @@
 // Width-128 decoder, backward (mlp128.h: the layer equations and layouts):
-//   k_mlp_bwd3       the δ chain and the weight gradients in one persistent
-//                    kernel, one slab of every layer per workgroup
-//   k_mlp_dw_reduce  the slab sum (k_mlp_bwd3's and k_mlp_trunk_fb's)
-// and dec128_bwd, the one host function that sequences them with the sparse
-// decoder's class-B kernel (k_mlp_trunk_fb: mlp128_trunk_fb.h, compiled here)
-// and the dfeat_ready event.
+//   k_mlp_bwd3<W>      the δ chain and the weight gradients in one persistent
+//                      kernel, one slab of every layer per workgroup
+//   k_mlp_bwd3<W, H2>  the same body on a part of the grid and the sparse
+//                      decoder's class-B body (mlp128_trunk_fb.h, compiled
+//                      here) on the rest: both sample classes in one launch
+//   k_mlp_dw_reduce    the slab sum
+// and dec128_bwd, the one host function that chooses between that launch and
+// the two it replaces (k_mlp_bwd3<W>, then k_mlp_trunk_fb) and sequences them
+// with the dfeat_ready event and the slab sum.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -38,8 +41,17 @@ __device__ __forceinline__ float dw_sum_range(const float *__restrict__ p, int64
     for (; sp < e; ++sp) v += p[sp * stride];
     return v;
 }
+//
+// cnt (or null; then no slabs_b): the slabs are the one-launch backward's
+// (k_mlp_bwd3<W, H2>), whose workgroups [0, nA) are class A's and [nA, G) class
+// B's, nA = bwd_split_na of the two counts as in that kernel: the elements
+// k_mlp_trunk_fb writes are summed over all G slabs, every other element over
+// the first nA only (a class-B slab's are not written and never read; nA = 0:
+// exact zeros) — quarters of that range, in order.
 __global__ __launch_bounds__(256) void k_mlp_dw_reduce(DwGrid g, const float *__restrict__ slabs, DwDst dst,
-                                                       int accumulate, const float *__restrict__ slabs_b) {
+                                                       int accumulate, const float *__restrict__ slabs_b,
+                                                       const int *__restrict__ cnt, const int *__restrict__ cnt_b,
+                                                       BwdSplitCost cost) {
     __shared__ float part[4][kDwRedEl];
     const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
     const int e = blockIdx.x * kDwRedEl + lane;
@@ -48,14 +60,19 @@ __global__ __launch_bounds__(256) void k_mlp_dw_reduce(DwGrid g, const float *__
 #pragma unroll
     for (int l = 1; l < 5; ++l) L += (e >= dst.elem_begin[l]);
     const int rel = in ? e - dst.elem_begin[L] : 0;
-    const int n_split = g.n_split[L];
+    const bool trunk_el = L < 2 || (L == 2 && (rel < 128 || rel == 129 * 128));  // k_mlp_trunk_fb's elements
+    int n_split = g.n_split[L];
+    if (cnt) {
+        const int64_t m_a = __builtin_amdgcn_readfirstlane(*cnt), m_b = __builtin_amdgcn_readfirstlane(*cnt_b);
+        const int n_a = bwd_split_na((m_a + kU - 1) / kU, (m_b + kU - 1) / kU, n_split, cost);
+        if (!trunk_el) n_split = n_a;
+    }
     const int64_t stride = g.slab_len[L];
     const int b = n_split * k / 4, en = n_split * (k + 1) / 4;
     float v = 0.0f;
     if (in) {
         v = dw_sum_range(slabs + g.slab_off[L] + rel, stride, b, en);
-        if (slabs_b && (L < 2 || (L == 2 && (rel < 128 || rel == 129 * 128))))
-            v += dw_sum_range(slabs_b + g.slab_off[L] + rel, stride, b, en);
+        if (slabs_b && trunk_el) v += dw_sum_range(slabs_b + g.slab_off[L] + rel, stride, b, en);
     }
     part[k][lane] = v;
     __syncthreads();
@@ -142,19 +159,22 @@ struct Bwd3Src {
 // sample (ip.gx, summed per ray by k_interp_rays_gx) and the embedding
 // scatter, summed over each leaf run of the unit first (k_interp_bwd's
 // scheme: lanes own (corner, dim), whole 64-B rows per atomic instruction).
+//
+// The body is a device function of its workgroup's place: workgroup `wg` of
+// the `n_wg` that share the m samples, writing slab `b` (k_mlp_bwd3<W> below:
+// the whole grid; k_mlp_bwd3<W, H2>: the grid's class-A part).
 template <bool W>
-__global__ __launch_bounds__(kF2Threads, 1) void k_mlp_bwd3(int64_t m, const float *__restrict__ img, Bwd3Src src,
-                                                            DwGrid g, float *__restrict__ slabs, InterpFuse ip,
-                                                            const int *__restrict__ m_dev) {
+__device__ __forceinline__ void mlp_bwd3_body(const unsigned wg, const unsigned n_wg, const int b, const int64_t m,
+                                              const float *__restrict__ img, const Bwd3Src &src, const DwGrid &g,
+                                              float *__restrict__ slabs, const InterpFuse &ip) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    if (m_dev) m = __builtin_amdgcn_readfirstlane(*m_dev);  // the sparse decoder's kept samples (<= m)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t n_tiles = (m + kCh - 1) / kCh * 2;  // CF tiles (32 samples)
     const int64_t tstride = n_tiles * kCfTile;
     const int64_t tb = tstride * 4;
     const int64_t n_units = (m + kU - 1) / kU;
-    const int64_t u0 = n_units * blockIdx.x / gridDim.x, u1 = n_units * (blockIdx.x + 1) / gridDim.x;
+    const int64_t u0 = n_units * wg / n_wg, u1 = n_units * (wg + 1) / n_wg;
     constexpr int kPer = W ? 4 : 8;  // units per round
     const int n_rounds = (int)((u1 - u0 + kPer - 1) / kPer);
     float *const slot = lds + kB3Slot, *const small = lds + kB3Small, *const xim = lds + kB3X;
@@ -167,7 +187,6 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_bwd3(int64_t m, const flo
     stage8(lds, img + kImgVec, kVecPad, wave, lane);
     wait_vm(0);
     raw_barrier();
-    const int b = blockIdx.x;
     const int i = lane & 31, h = lane >> 5;
     if (!W || wave < 4) {
         // ================= chain wave c
@@ -466,6 +485,48 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_bwd3(int64_t m, const flo
     }
 }
 
+template <bool W>
+__global__ __launch_bounds__(kF2Threads, 1) void k_mlp_bwd3(int64_t m, const float *__restrict__ img, Bwd3Src src,
+                                                            DwGrid g, float *__restrict__ slabs, InterpFuse ip,
+                                                            const int *__restrict__ m_dev) {
+    if (m_dev) m = __builtin_amdgcn_readfirstlane(*m_dev);  // the sparse decoder's kept samples (<= m)
+    mlp_bwd3_body<W>(blockIdx.x, gridDim.x, blockIdx.x, m, img, src, g, slabs, ip);
+}
+
+// ---------------------------------------------------------------------------
+// Both sample classes of the sparse decoder in ONE launch: workgroups
+// [0, nA) run k_mlp_bwd3<true>'s body over nA shares of class A's units,
+// workgroups [nA, G) run k_mlp_trunk_fb<H2>'s body over G − nA shares of class
+// B's, nA = bwd_split_na of the two device counts (psvo_common.h: the modelled
+// finish times meet).  As two launches each class quantised on its own over
+// all G workgroups (8 rounds of 7,875 units, then 3 of 2,750 with the trunk
+// kernel's fixed cost on the critical path) and the chip waited for both
+// tails at a kernel boundary.  Nothing passes between workgroups and none
+// waits for another: the result does not depend on the dispatch order, only
+// the balance assumes one workgroup per CU (as the two kernels do).  Workgroup
+// b writes slab b of ONE slab set: a class-B workgroup only the elements
+// k_mlp_trunk_fb writes — k_mlp_dw_reduce (n_a) reads no others of it.
+struct TrunkSrc {
+    const int *m_dev;
+    const float *g_sdf, *feat, *h2;
+    const int *h2_src;
+};
+template <bool W, bool H2>
+__global__ __launch_bounds__(kF2Threads, 1) void k_mlp_bwd3(int64_t m, const float *__restrict__ img, Bwd3Src src,
+                                                            DwGrid g, float *__restrict__ slabs, InterpFuse ip,
+                                                            const int *__restrict__ m_dev, TrunkSrc tk,
+                                                            InterpFuse ip_b, BwdSplitCost cost) {
+    static_assert(W, "the two-class launch is a training launch");
+    const int n_wg = gridDim.x, b = blockIdx.x;
+    if (m_dev) m = __builtin_amdgcn_readfirstlane(*m_dev);
+    const int64_t m_b = __builtin_amdgcn_readfirstlane(*tk.m_dev);
+    const int n_a = bwd_split_na((m + kU - 1) / kU, (m_b + kU - 1) / kU, n_wg, cost);
+    if (b < n_a)
+        mlp_bwd3_body<true>(b, n_a, b, m, img, src, g, slabs, ip);
+    else
+        mlp_trunk_fb_body<H2>(b - n_a, n_wg - n_a, b, m_b, img, tk.g_sdf, tk.feat, g, slabs, ip_b, tk.h2, tk.h2_src);
+}
+
 // k_mlp_bwd3: one workgroup per CU (at most one per round of 4 units), each
 // writing a slab of every layer
 int bwd3_grid(int64_t m) {
@@ -512,6 +573,8 @@ int dec128_bwd(hipStream_t st, int64_t m, const float *feat, const float *images
     PSVO_REQUIRE(tb == nullptr || (gw[0] != nullptr && tb->m_dev && tb->g_sdf && tb->feat),
                  "mlp_bwd: the trunk backward needs the weight-gradient path and its inputs");
     float *slabs_b = nullptr;
+    const int *cnt_a = nullptr, *cnt_b = nullptr;  // set: the one-launch backward's slabs
+    const BwdSplitCost cost = bwd_split_cost();
     auto reduce = [&](float *slabs, hipStream_t rs) {
         DwDst d;
         int e = 0;
@@ -525,7 +588,7 @@ int dec128_bwd(hipStream_t st, int64_t m, const float *feat, const float *images
         }
         d.elem_begin[5] = e;
         psvo::launch(k_mlp_dw_reduce, dim3(div_up(e, kDwRedEl)), dim3(256), 0, rs, g, slabs, d, accumulate,
-                     static_cast<const float *>(slabs_b));
+                     static_cast<const float *>(slabs_b), cnt_a, cnt_b, cost);
         return check_launch("mlp_dw_reduce");
     };
     Bwd3Src src{rgb, g_sdf, g_rgb, feat, masks, act, dfeat, x_src};
@@ -553,7 +616,27 @@ int dec128_bwd(hipStream_t st, int64_t m, const float *feat, const float *images
     const bool trunk_last = tb && m > 0;
     bool bound = false;
     const hipEvent_t bind_ev = bind_env ? dfeat_ready : nullptr;  // offered to the last kernel only
-    if (m > 0) {
+    // both classes in one launch (k_mlp_bwd3<W, H2>); two launches: no split of one workgroup, the
+    // count on the host only, or asked for (PSVO_PATH_BWD_TWO_LAUNCH)
+    const bool one_launch = trunk_last && grid >= 2 && m_dev && !tb->two_launch;
+    if (one_launch) {
+        PSVO_REQUIRE(!tb->h2 || tb->src, "mlp_bwd: the trunk's h2 rows need their source index");
+        cnt_a = m_dev;
+        cnt_b = tb->m_dev;
+        const TrunkSrc tk{tb->m_dev, tb->g_sdf, tb->feat, tb->h2, tb->src};
+        const InterpFuse ip_a = ip ? *ip : InterpFuse{}, ip_b = tb->ip ? *tb->ip : InterpFuse{};
+        constexpr int kLdsAb = kLdsBwd3 > kLdsTrunk ? kLdsBwd3 : kLdsTrunk;
+        psvo::StopBind sb(bind_ev);
+        if (tb->h2)
+            launch_lds<k_mlp_bwd3<true, true>>(dim3(grid), dim3(kF2Threads), kLdsAb, st, m, images, src, g, slabs,
+                                               ip_a, m_dev, tk, ip_b, cost);
+        else
+            launch_lds<k_mlp_bwd3<true, false>>(dim3(grid), dim3(kF2Threads), kLdsAb, st, m, images, src, g, slabs,
+                                                ip_a, m_dev, tk, ip_b, cost);
+        bound = sb.consumed();
+        const int rc = check_launch("mlp_bwd3 (both classes)");
+        if (rc) return rc;
+    } else if (m > 0) {
         psvo::StopBind sb(trunk_last ? nullptr : bind_ev);
         launch_lds<k_mlp_bwd3<true>>(dim3(grid), dim3(kF2Threads), kLdsBwd3, st, m, images, src, g, slabs,
                                      ip ? *ip : InterpFuse{}, m_dev);
@@ -563,7 +646,7 @@ int dec128_bwd(hipStream_t st, int64_t m, const float *feat, const float *images
     } else if (hipMemsetAsync(slabs, 0, (size_t)slab_floats * sizeof(float), st) != hipSuccess) {
         return set_error(PSVO_E_LAUNCH, "mlp_bwd: memset failed");
     }
-    if (trunk_last) {  // the sparse decoder's class B: the trunk forward + backward, its own slabs
+    if (trunk_last && !one_launch) {  // the sparse decoder's class B: the trunk forward + backward, its own slabs
         slabs_b = slabs + slab_floats;
         PSVO_REQUIRE(!tb->h2 || tb->src, "mlp_bwd: the trunk's h2 rows need their source index");
         psvo::StopBind sb(bind_ev);

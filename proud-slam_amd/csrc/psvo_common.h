@@ -515,7 +515,50 @@ struct TrunkBwd {
     const float *h2 = nullptr;  // or: the step's h2 rows (H2Rows) and each class-B sample's row —
     const int *src = nullptr;   // the W2 layer is read instead of recomputed; feat then holds the
                                 // step's rows too (x of sample s: row src[s])
+    bool two_launch = false;    // k_mlp_trunk_fb after k_mlp_bwd3 (PSVO_PATH_BWD_TWO_LAUNCH), not one launch
 };
+
+// The one-launch backward's split (mlp_bwd.hip k_mlp_bwd3<W, H2>): of n_wg
+// workgroups the first nA take class A's units_a 16-sample units, the other
+// n_wg − nA class B's units_b, each class split evenly (share w of n: units
+// [units·w / n, units·(w + 1) / n)) and run in rounds of four units.  nA
+// minimises the modelled finish time
+//     max(R_A · a, R_B · b + b0),   R = ceil(ceil(units / n) / 4),
+// a : b the per-round cycles of the two bodies and b0 class B's forward of
+// round 0, which runs before its loop (s_memtime stamps of both roles inside
+// the one launch at the flagship's mix, in k cycles: 75 and 35 — a FULL
+// class-B round; k_mlp_trunk_fb's own mean of 26 k over its 3 rounds counts a
+// last round of 2 or 3 units; profiles/bwd_ab_stamps.txt).  R_A does not grow
+// with nA and R_B does not shrink: the minimum is at the crossing, found by
+// bisection — integers only, so the kernel's workgroups, the slab sum and the
+// host agree.  An empty class gets no workgroup, a present one at least one;
+// n_wg == 1 with both present has no split (the caller launches twice).
+struct BwdSplitCost {
+    int a, b, b0;
+};
+constexpr BwdSplitCost kBwdSplitCost = {75, 35, 16};
+BwdSplitCost bwd_split_cost();  // kBwdSplitCost unless psvo_debug_set_bwd_split changed it (capi.cpp)
+__host__ __device__ inline int64_t bwd_split_rounds(int64_t units, int n) { return ((units + n - 1) / n + 3) / 4; }
+__host__ __device__ inline int bwd_split_na(int64_t units_a, int64_t units_b, int n_wg, BwdSplitCost c) {
+    if (units_a <= 0) return 0;
+    if (units_b <= 0 || n_wg < 2) return n_wg;
+    auto t_a = [&](int n) { return bwd_split_rounds(units_a, n) * c.a; };
+    auto t_b = [&](int n) { return bwd_split_rounds(units_b, n_wg - n) * c.b + c.b0; };
+    int lo = 1, hi = n_wg - 1;  // the smallest n in [1, n_wg − 1] with t_a(n) <= t_b(n), else n_wg − 1
+    while (lo < hi) {
+        const int mid = (lo + hi) / 2;
+        if (t_a(mid) <= t_b(mid))
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    // left of the crossing class A finishes last, from it on class B (or lo is the last candidate)
+    auto t = [&](int n) {
+        const int64_t ta = t_a(n), tb = t_b(n);
+        return ta > tb ? ta : tb;
+    };
+    return lo > 1 && t(lo - 1) < t(lo) ? lo - 1 : lo;
+}
 // grads: the ten parameter gradients gW1, gb1, ..., gW5, gb5 (the order of
 // psvo_map_desc::dec); a null array or null entries: the δ chain / dfeat only
 // (frozen decoder).  The weights themselves are not read: `images` holds them.

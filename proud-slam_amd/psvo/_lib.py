@@ -83,6 +83,8 @@ _SIGNATURES = {
     "psvo_engine_select_stats": (_i32, [_vp, _vp, _vp, _i32]),
     "psvo_engine_gate_stream": (_i32, [_vp, _vp]),
     "psvo_debug_set_lookback": (_i32, [_i32, _i32, _i32]),
+    "psvo_debug_set_bwd_split": (_i32, [_i32, _i32, _i32]),
+    "psvo_debug_bwd_split": (_i32, [_i64, _i64, _i32]),
     "psvo_debug_set_pixel_draw": (_i32, [_i32]),
     "psvo_debug_lb_helps": (_i32, [_vp, _i32]),
     "psvo_debug_select_samples": (_i32, [_vp, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _i32] + [_vp] * 7

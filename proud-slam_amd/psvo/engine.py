@@ -378,7 +378,7 @@ class MappingEngine:
         L.call("psvo_map_adam_ex", self.handle, L.stream_of(self.emb.device), ctypes.addressof(self.desc),
                self.step_no, 1 if marked else 0)
 
-    PATH_QUERY_SPLIT, PATH_PADDED, PATH_DENSE_DECODER, PATH_INTERP_PASS = 1, 2, 4, 8
+    PATH_QUERY_SPLIT, PATH_PADDED, PATH_DENSE_DECODER, PATH_INTERP_PASS, PATH_BWD_TWO_LAUNCH = 1, 2, 4, 8, 16
 
     def set_paths(self, paths):
         """Run the alternative production kernels on this single-GPU engine
@@ -387,7 +387,10 @@ class MappingEngine:
         copy and in-step loss normalisers; PATH_DENSE_DECODER — the width-128
         decoder on every sample instead of the sparse decoder;
         PATH_INTERP_PASS — the device-sized forward's interpolation as a pass
-        of its own instead of inside the sdf trunk (psvo_engine_set_paths)."""
+        of its own instead of inside the sdf trunk; PATH_BWD_TWO_LAUNCH — the
+        sparse decoder's backward as two launches (the loss-only samples'
+        trunk kernel after k_mlp_bwd3) instead of one launch divided between
+        the two sample classes (psvo_engine_set_paths)."""
         L.call("psvo_engine_set_paths", self.handle, int(paths))
 
     def select_stats(self, reset=False):

@@ -2,7 +2,11 @@
 round — s_memtime stamps of the lib/diag/libpsvo_stamps.so build (`make -C
 proud-slam_amd/csrc stamps`), recorded by the last launch of a short
 bench.py run (config B).  Read the SHARES of the segments: the stamps fence
-the code.  Usage: trunk_stamps.py [bench args...]"""
+the code.  The one-launch backward (k_mlp_bwd3<W, H2>) stamps its class-A
+workgroups as bwd3 and its class-B workgroups as trunk_fb, so both roles'
+rounds read the same way in it as in the two kernels (PSVO_BWD_TWO_LAUNCH=1).
+PSVO_STAMPS_LIB: another stamps build (e.g. the parent commit's, for a
+side-by-side in one job).  Usage: trunk_stamps.py [bench args...]"""
 import ctypes
 import os
 import sys
@@ -10,7 +14,7 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIAG = os.path.join(ROOT, "proud-slam_amd", "lib", "diag", "libpsvo_stamps.so")
+DIAG = os.environ.get("PSVO_STAMPS_LIB") or os.path.join(ROOT, "proud-slam_amd", "lib", "diag", "libpsvo_stamps.so")
 os.environ["PSVO_LIB_PATH"] = DIAG
 sys.path.insert(0, ROOT)
 
@@ -38,8 +42,14 @@ def report(st, kern, last, roles):  # st: [wg][wave][round][stamp]
         v = st[:, list(waves)].reshape(-1, 16)
         ok = (v[:, 0] > 0) & (v[:, last] > 0)
         v = v[ok]
-        tot = (v[:, last] - v[:, 0]).mean()
-        print(f"{kern} {role}: {len(v)} wave-rounds, mean round {tot:.0f} cycles", file=sys.stderr)
+        if not len(v):
+            print(f"{kern} {role}: no stamps", file=sys.stderr)
+            continue
+        rnd = (v[:, last] - v[:, 0]).astype(np.float64)
+        tot = rnd.mean()
+        print(f"{kern} {role}: {len(v)} wave-rounds, mean round {tot:.0f} cycles (min {rnd.min():.0f}, p10 "
+              f"{np.percentile(rnd, 10):.0f}, median {np.median(rnd):.0f}, p90 {np.percentile(rnd, 90):.0f}, max "
+              f"{rnd.max():.0f})", file=sys.stderr)
         for nm, a, b in segs:
             good = (v[:, a] > 0) & (v[:, b] > 0)
             d = (v[good, b] - v[good, a]).astype(np.float64)
