@@ -5,6 +5,7 @@
 
 #include "psvo_common.h"
 #include "lookback.h"
+#include "query.h"
 
 namespace psvo {
 
@@ -71,9 +72,11 @@ extern "C" int psvo_debug_set_lookback(int mask, int spin_bound, int delay_us) {
 
 extern "C" int psvo_debug_lb_helps(int64_t *out3, int reset) {
     PSVO_REQUIRE(out3, "debug_lb_helps: null argument");
-    const int rc = psvo::lb_helps_query(out3, reset != 0);
-    if (rc != PSVO_OK) return rc;
-    return psvo::lb_helps_select(out3 + 2, reset != 0);
+    // {traversal, sampler, selection}: one counter per translation unit
+    int rc = psvo::lb_helps_trace(out3, reset != 0);
+    if (rc == PSVO_OK) rc = psvo::lb_helps_sample(out3 + 1, reset != 0);
+    if (rc == PSVO_OK) rc = psvo::lb_helps_select(out3 + 2, reset != 0);
+    return rc;
 }
 
 // tests only: the engine-internal selection / fused compositing entry points, arguments passed straight through

@@ -16,6 +16,7 @@
 
 #include "lookback.h"
 #include "psvo_common.h"
+#include "query.h"
 #include "select_common.h"
 
 namespace psvo {

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "psvo_common.h"
+#include "query.h"
 
 #pragma clang fp contract(off)
 
@@ -29,7 +30,7 @@ namespace {
 
 enum { kSumColor = 0, kSumDepth, kNValid, kNFront, kNSdf, kSqFs, kSqSdf, kNSums = 8 };
 enum { kFlagColor = 1, kFlagDepth = 2, kFlagSdf = 4 };
-static_assert(kNValid == 2 && kNFront == 3 && kNSdf == 4, "svo_query.hip k_dist_smax writes these slots");
+static_assert(kNValid == 2 && kNFront == 3 && kNSdf == 4, "query_dist.hip k_dist_smax writes these slots");
 // out[] layout (PSVO_CRIT_* in psvo.h)
 enum { kOutLoss = 0, kOutColor, kOutDepth, kOutFs, kOutSdf, kOutFsW, kOutSdfW, kOutCColor, kOutCDepth, kOutCFs,
        kOutCSdf };
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(256) void k_crit_counts(int64_t r_hit, int s_max, f
 }
 
 // data parallel: this rank's count words for the query's second all-gather
-// (psvo_common.h dist_counts) — one wave per local hit row (sampler rows,
+// (query.h dist_counts) — one wave per local hit row (sampler rows,
 // valid prefix ray_ns), integer atomics (exact, order-free); the padding's
 // terms stay per ray so the union S_max can be applied after the gather
 __global__ __launch_bounds__(256) void k_dist_counts(const int *__restrict__ stats, const int *__restrict__ rank_ray,

@@ -1,5 +1,5 @@
 // The decoder's width dispatch and C ABI (include/psvo.h psvo_mlp_*): every
-// call goes to dec128_* (mlp_fwd.hip, mlp_bwd.hip, mlp_trunk_fb.hip) or
+// call goes to dec128_* (mlp_fwd.hip, mlp_bwd.hip, mlp128_trunk_fb.h) or
 // dec256_* (mlp256.hip), which check their own arguments and launch their
 // own kernels — nothing is launched from here.
 #include <hip/hip_runtime.h>

@@ -12,6 +12,7 @@
 
 #include "psvo_common.h"
 #include "lookback.h"
+#include "query.h"
 
 namespace psvo {
 

@@ -262,7 +262,7 @@ int query_enqueue(psvo_engine *e, hipStream_t st, QuerySet &q, const psvo_map_de
     q.compacted = false;
     if (!x.on()) {  // the sampler's scan does the read-back (and, given the GT depths, the loss normalisers)
         psvo::SampleCounts sc{};
-        // the per-ray counts pack into 12-bit fields (svo_query.hip pack_counts):
+        // the per-ray counts pack into 12-bit fields (query_sample.hip pack_counts):
         // rows that may hold more than 4095 samples count in the step instead (k_crit_counts)
         const bool counts = counts_gt != nullptr && max_steps <= 4095;
         if (counts) {

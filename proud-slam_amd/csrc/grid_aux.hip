@@ -47,7 +47,7 @@ __device__ __forceinline__ int lanes_below(uint64_t m) {
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
-// intersect_gpu.cu:75-140 — the comparisons of svo_query.hip's ray_aabb_nb:
+// intersect_gpu.cu:75-140 — the comparisons of query_trace.hip's ray_aabb_nb:
 // the reference's early-exit tests in order, the verdict accumulated so the
 // wave runs one basic block per box instead of three divergent exits
 __device__ __forceinline__ bool slab(const float o[3], const float inv[3], const float c[3], float half,

@@ -61,7 +61,7 @@ namespace psvo {
 constexpr int kLbSpinMax = 1 << 18;
 constexpr int kLbHelpAfter = 16;   // re-reads between checks of the missing producers' started granules
 constexpr uint64_t kLbHelpAfterTicks = 10000;  // kLbHelpAfterUs = 100 µs of waiting (s_memrealtime: 100 MHz)
-// (kLbFlagTimeout, PSVO_STAT_FLAGS bit 3: psvo_common.h, with the word's other bits)
+// (kLbFlagTimeout, PSVO_STAT_FLAGS bit 3: query.h, with the word's other bits)
 constexpr int kLbDone = -1, kLbFail = -2;  // lb_scan_help's results (≥ 0: the block to help)
 
 template <unsigned MAXMASK>

@@ -30,6 +30,7 @@
 
 #include "interp_load.h"
 #include "psvo_common.h"
+#include "query.h"
 #include "select_common.h"
 
 namespace psvo {

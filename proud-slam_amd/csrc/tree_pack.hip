@@ -150,7 +150,7 @@ __global__ __launch_bounds__(kPtThreads) void k_pt_emit(int level, const float *
     }
 }
 
-// The traversal's start level (svo_query.hip, top_start): the deepest level
+// The traversal's start level (query_trace.hip, top_start): the deepest level
 // m >= 2 such that the records above it — [0, meta[m].first), breadth-first —
 // number at most kTopMax and hold no leaf (side 1).  The root's spare word
 // gets that count | m << 16 (0: start at the root); each other record among

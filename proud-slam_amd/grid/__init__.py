@@ -7,9 +7,9 @@ Same names, argument order, shapes, dtypes, output allocation and
 precondition errors (TORCH_CHECK → RuntimeError, include/utils.h:10-33) as
 intersect.cpp / sample.cpp.  Kernel launch failures raise instead of the
 reference's exit(-1) (cuda_utils.h:37-48).  The two render-path functions
-run on csrc/svo_query.hip; the five off the path (ball / aabb / triangle
-intersection, uniform sampling — csrc/grid_aux.hip — and build_octree, on
-the host in csrc/grid_octree.cpp) keep the reference's semantics for code
+run on csrc/query_trace.hip and query_sample.hip; the five off the path
+(ball / aabb / triangle intersection, uniform sampling — csrc/grid_aux.hip —
+and build_octree, on the host in csrc/grid_octree.cpp) keep the reference's semantics for code
 such as src/variations/test_aabb.py.
 """
 from __future__ import annotations

@@ -1,5 +1,5 @@
 """CPU checks of the data-parallel engine's exchange protocol (include/psvo.h
-psvo_engine_set_exchange; csrc/svo_query.hip k_dist_*).
+psvo_engine_set_exchange; csrc/query_dist.hip k_dist_*).
 
 1. Sufficiency: a rank samples its rows of the union batch's [200, K', P]
    layout from its own hit lists plus (a) the slot-0 rows' hit COUNTS (their
