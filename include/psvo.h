@@ -415,6 +415,31 @@ int psvo_mesh_mc_emit(void *stream, int64_t n_vox, int res, float voxel_size, co
 int64_t psvo_mesh_vox_map_slots(int64_t n_vox);
 int psvo_mesh_vertex_rows(void *stream, int64_t n_vox, const float *voxels, int64_t n_verts, const float *verts,
                           float voxel_size, int *table, int *row);
+/* Mesh cleaning (csrc/mesh_clean.hip; create_mesh's clean_mseh branch,
+ * mesh_util.py:60-78 and :140-146), three stages.
+ * Back-projection: out f64[n,3] = R·(dirs[i]·depth[i]) + t, pose = the rows
+ * [R|t] (12 floats); every product and sum rounded to fp32 in the order of the
+ * depth-frame integration's pixel keys, then widened.  Every pixel is written. */
+int psvo_mesh_depth_points(void *stream, int64_t n, const float *depth, const float *dirs, const float *pose,
+                           double *out);
+/* downsample_points (open3d voxel_down_sample as the project restates it):
+ * key = floor((p − min)/cell) per axis; out f64[≤ n,3] = one row per distinct
+ * key in ascending (x, y, z) key order, (0 + p_i0 + p_i1 + …)/count with the
+ * members added in input order (np.unique + np.add.at, bit for bit).  count
+ * (device i64): the rows written, or a negative word when a coordinate is not
+ * finite or an axis spans 2²¹ cells or more — psvo_mesh_points_status(word)
+ * (host) turns that word into the error. */
+int64_t psvo_mesh_downsample_workspace_bytes(int64_t n);
+int psvo_mesh_points_downsample(void *stream, int64_t n, const double *points, double cell, void *workspace,
+                                double *out, int64_t *count);
+int psvo_mesh_points_status(int64_t word);
+/* hit u8[n_verts]: 1 where some point lies within radius of the vertex,
+ * (dx·dx + dy·dy) + dz·dz ≤ r·r with d = double(vert) − point, in fp64;
+ * status (device i64): 0, or a negative word for psvo_mesh_points_status.
+ * m = 0: all zeros; n_verts = 0: nothing is written but status. */
+int64_t psvo_mesh_ball_workspace_bytes(int64_t m);
+int psvo_mesh_ball_any(void *stream, int64_t m, const double *points, int64_t n_verts, const float *verts,
+                       double radius, void *workspace, uint8_t *hit, int64_t *status);
 
 /* ---- optimiser ------------------------------------------------------- */
 /* One Adam step (torch.optim.Adam, amsgrad off) over n_tensors f32 tensors:

@@ -124,6 +124,12 @@ _SIGNATURES = {
     "psvo_mesh_mc_emit": (_i32, [_vp, _i64, _i32, _f32] + [_vp] * 7),
     "psvo_mesh_vox_map_slots": (_i64, [_i64]),
     "psvo_mesh_vertex_rows": (_i32, [_vp, _i64, _vp, _i64, _vp, _f32, _vp, _vp]),
+    "psvo_mesh_depth_points": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "psvo_mesh_downsample_workspace_bytes": (_i64, [_i64]),
+    "psvo_mesh_points_downsample": (_i32, [_vp, _i64, _vp, _f64, _vp, _vp, _vp]),
+    "psvo_mesh_points_status": (_i32, [_i64]),
+    "psvo_mesh_ball_workspace_bytes": (_i64, [_i64]),
+    "psvo_mesh_ball_any": (_i32, [_vp, _i64, _vp, _i64, _vp, _f64, _vp, _vp, _vp]),
     "psvo_pose_grad": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "psvo_criterion_depth_filter": (_i32, [_vp, _i64, _i32] + [_vp] * 7),
     "psvo_criterion_sums_ex": (_i32, [_vp, _i64, _i32, _i32, _f32, _f32] + [_vp] * 11),

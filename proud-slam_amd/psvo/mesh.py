@@ -11,6 +11,13 @@ read-back for the output sizes) → a hash lookup of each vertex's voxel →
 point features → the decoder for the colours; everything stays in HBM until
 the mesh is returned.  The triangulation rule and its parity status are in
 csrc/mesh.hip and DESIGN.md §6d.
+
+create_mesh's clean_mseh branch (mesh_util.py:60-78, :140-146) stays on the
+device too (csrc/mesh_clean.hip): the depth frame is back-projected, the
+accumulated depth points are re-binned into 1-cm cells (DepthPointSet, bit for
+bit the host's np.unique + np.add.at means) and the faces without a vertex
+within voxel_size / 2 of a depth point are dropped (a sorted uniform grid in
+place of the cKDTree); clean="host" keeps the numpy / scipy path for A/B runs.
 """
 from __future__ import annotations
 
@@ -162,6 +169,96 @@ def vertex_rows(voxels, verts, voxel_size):
     return rows
 
 
+def _pose_rows(pose, dev):
+    """The rows [R|t] of a pose (anything 3×4 or 4×4) as 12 device floats."""
+    p = torch.as_tensor(pose, dtype=torch.float32).to(dev)
+    if p.dim() != 2 or p.shape[0] < 3 or p.shape[1] != 4:
+        raise ValueError(f"pose must be [3|4, 4], got {tuple(p.shape)}")
+    return p[:3].contiguous()
+
+
+@torch.no_grad()
+def depth_points_device(pose, depth, rays_d):
+    """get_valid_points' back-projection (mesh_util.py:60-66): device f64 [n, 3]
+    world points R·(rays_d·depth) + t of every pixel (depth 0 included: the
+    camera centre), each product and sum rounded to fp32, then widened."""
+    rays_d = rays_d.reshape(-1, 3).float().contiguous()
+    dev = rays_d.device
+    depth = torch.as_tensor(depth).to(dev).reshape(-1).float().contiguous()
+    if depth.shape[0] != rays_d.shape[0]:
+        raise ValueError(f"depth has {depth.shape[0]} pixels, rays_d {rays_d.shape[0]}")
+    out = torch.empty((depth.shape[0], 3), dtype=torch.float64, device=dev)
+    L.call("psvo_mesh_depth_points", L.stream_of(dev), depth.shape[0], depth, rays_d, _pose_rows(pose, dev), out)
+    return out
+
+
+def _workspace(name, n, dev):
+    size = int(getattr(L.lib(), name)(n))
+    if size < 0:
+        raise L.PsvoError(f"{name}({n}) failed")
+    return torch.empty(size, dtype=torch.uint8, device=dev)
+
+
+@torch.no_grad()
+def downsample_points_device(points, voxel_size=0.01):
+    """MeshExtractor.downsample_points on the device, bit for bit: device f64
+    [K, 3], the mean of the points in each occupied cell in ascending cell
+    order.  One 8-byte read-back (K).  Raises on a non-finite coordinate or an
+    extent of 2²¹ cells or more."""
+    p = points.reshape(-1, 3).double().contiguous()
+    n, dev = p.shape[0], p.device
+    if n == 0:
+        return p
+    out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    L.call("psvo_mesh_points_downsample", L.stream_of(dev), n, p, float(voxel_size),
+           _workspace("psvo_mesh_downsample_workspace_bytes", n, dev), out, count)
+    k = int(count.cpu())
+    L.call("psvo_mesh_points_status", k)
+    return out[:k]
+
+
+@torch.no_grad()
+def ball_any_device(points, verts, radius):
+    """Device bool [V]: whether some point (f64 [M, 3]) lies within `radius` of
+    the vertex (f32 [V, 3]) — cKDTree.query_ball_point(...) > 0, the distance
+    test in fp64.  One 8-byte read-back (the points' status)."""
+    verts = verts.reshape(-1, 3).float().contiguous()
+    dev = verts.device
+    p = points.to(dev).reshape(-1, 3).double().contiguous()
+    m, v = p.shape[0], verts.shape[0]
+    hit = torch.empty(v, dtype=torch.uint8, device=dev)
+    status = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = _workspace("psvo_mesh_ball_workspace_bytes", m, dev) if m > 0 and v > 0 else None
+    L.call("psvo_mesh_ball_any", L.stream_of(dev), m, p, v, verts, float(radius), ws, hit, status)
+    L.call("psvo_mesh_points_status", int(status.cpu()))
+    return hit.bool()
+
+
+class DepthPointSet:
+    """The accumulated, down-sampled depth points of get_valid_points
+    (mesh_util.py:68-78) as device f64 [M, 3]: add_frame concatenates the old
+    means and a frame's points and re-bins them all (the reference's
+    unweighted re-mean; the cells' origin moves with the minimum)."""
+
+    def __init__(self, device="cuda", voxel_size=0.01):
+        self.device, self.voxel_size = torch.device(device), voxel_size
+        self.points = None
+
+    def add_frame(self, pose, depth, rays_d):
+        pts = depth_points_device(pose, depth, rays_d.to(self.device))
+        if self.points is not None:
+            pts = torch.cat([self.points, pts], 0)
+        self.points = downsample_points_device(pts, self.voxel_size)
+        return self.points
+
+    def numpy(self):
+        return None if self.points is None else self.points.cpu().numpy()
+
+    def clear(self):
+        self.points = None
+
+
 class Mesh:
     """The fields create_mesh fills in the reference's open3d TriangleMesh
     (mesh_util.py:135-146): vertices (offset applied), triangles,
@@ -182,9 +279,11 @@ def _vertex_normals(verts, faces):
     f = faces.long()
     a, b, c = verts[f[:, 0]], verts[f[:, 1]], verts[f[:, 2]]
     fn = torch.cross(b - a, c - a, dim=-1)
+    # accumulating index_put_ sorts the indices and adds each vertex's faces in
+    # order (corner 0's faces, then corner 1's, then corner 2's): the same bits
+    # on every call, which index_add_'s atomics do not give
     vn = torch.zeros_like(verts)
-    for k in range(3):
-        vn.index_add_(0, f[:, k], fn)
+    vn.index_put_((f.t().reshape(-1),), fn.repeat(3, 1), accumulate=True)
     return vn / vn.norm(dim=-1, keepdim=True).clamp_min(1e-12)
 
 
@@ -194,7 +293,38 @@ class MeshExtractor:
     def __init__(self, args):
         self.voxel_size = args.mapper_specs["voxel_size"]
         self.rays_d = None
-        self.depth_points = None
+        self._points = DepthPointSet()   # the one copy of the accumulated depth points (device)
+        self._rays_dev = (None, None)    # (the rays_d it was made from, its device copy)
+
+    @property
+    def depth_points(self):
+        """The accumulated depth points as numpy f64 [M, 3] (a download), or None."""
+        return self._points.numpy()
+
+    @depth_points.setter
+    def depth_points(self, pts):
+        self._points.points = None if pts is None else torch.from_numpy(
+            np.ascontiguousarray(pts, dtype=np.float64)).to(self._points.device)
+
+    def _rays_on(self, dev):
+        src, cached = self._rays_dev
+        if src is not self.rays_d or cached.device != dev:
+            cached = torch.as_tensor(self.rays_d).to(dev).float().contiguous()
+            self._rays_dev = (self.rays_d, cached)
+        return cached
+
+    @torch.no_grad()
+    def valid_points_device(self, frame_poses, depth_maps, dev):
+        """get_valid_points on the device: device f64 [M, 3]."""
+        rays = self._rays_on(dev)
+        if isinstance(frame_poses, list):
+            pts = torch.cat([depth_points_device(frame_poses[i], depth_maps[i], rays)
+                             for i in range(0, len(frame_poses), 5)], 0)
+            return downsample_points_device(pts)
+        self._points.device = dev
+        if self._points.points is not None and self._points.points.device != dev:
+            self._points.points = self._points.points.to(dev)
+        return self._points.add_frame(frame_poses, depth_maps, rays)
 
     @torch.no_grad()
     def linearize_id(self, xyz, n_xyz):
@@ -244,7 +374,12 @@ class MeshExtractor:
 
     @torch.no_grad()
     def create_mesh(self, decoder, map_states, voxel_size, voxels, frame_poses=None, depth_maps=None,
-                    clean_mseh=False, require_color=False, offset=-10, res=8):
+                    clean_mseh=False, require_color=False, offset=-10, res=8, clean="device"):
+        """clean (with clean_mseh): "device" keeps the faces with a vertex within
+        voxel_size/2 of a depth point on the device (csrc/mesh_clean.hip);
+        "host" is the reference's numpy + cKDTree path, for A/B runs."""
+        if clean not in ("device", "host"):
+            raise ValueError(f"clean must be 'device' or 'host', got {clean!r}")
         centres, _, _ = _states(map_states)
         _, sdf = lattice_scores(decoder, map_states, voxel_size, res, with_rgb=False)
         verts, faces = marching_cubes_device(centres, sdf, self.voxel_size, res)
@@ -253,8 +388,12 @@ class MeshExtractor:
             rows = vertex_rows(torch.as_tensor(voxels).to(verts.device), verts, self.voxel_size)
             colours = point_colours(decoder, map_states, verts, rows, voxel_size)
         normals = _vertex_normals(verts, faces)
+        if clean_mseh and clean == "device":
+            hit = ball_any_device(self.valid_points_device(frame_poses, depth_maps, verts.device), verts,
+                                  voxel_size * 0.5)
+            faces = faces[hit[faces.long()].any(-1)]
         v_np, f_np = verts.cpu().numpy(), faces.cpu().numpy()
-        if clean_mseh:
+        if clean_mseh and clean == "host":
             from scipy.spatial import cKDTree
             kdtree = cKDTree(self.get_valid_points(frame_poses, depth_maps))
             hit = kdtree.query_ball_point(v_np, voxel_size * 0.5, workers=12, return_length=True) > 0
