@@ -987,6 +987,44 @@ int64_t psvo_dtree_frame_workspace_bytes(int h, int w);
 int psvo_dtree_insert_depth(void *tree, void *stream, int h, int w, const float *depth, const float *dirs_cam,
                             const float *pose34, float voxel_size, int64_t *stats_out /* host, or NULL */);
 
+/* ---- keyframe covisibility (csrc/covis.hip) ----------------
+ * The visible set V(frame, tree) of a depth frame: the node ids of the leaf
+ * voxels some ray of the frame sees, as a bitset of u32 words — bit v & 31 of
+ * word v >> 5, psvo_visibility_words words per set, bits at and beyond
+ * n_nodes zero.  Node ids are creation-ordered and never renumbered, so a
+ * set computed on a smaller tree stays valid zero-extended.
+ * Rays: the pixels (y, x) of the h x w image with y % px_step == 0 and
+ * x % px_step == 0 and depth > 0 (a NaN depth: no ray).  Origin t, direction
+ * d_j = (c0·R[j][0] + c1·R[j][1]) + c2·R[j][2] with c = dirs_cam[pixel] and
+ * [R | t] the frame's row-major pose34, every product and sum rounded to
+ * fp32 on its own (no FMA), not normalised: a ray parameter is a z-depth.
+ * Leaf v is in the set iff some ray's walk emits it (intersect_gpu.cu:191-270:
+ * a node is tested iff its parent passed the slab test; the comparisons of
+ * psvo_ray_intersect_sorted on the same values) with
+ * t_in <= depth + truncation (one fp32 add) and !(t_in > max_distance).
+ * There is NO cap on the leaves per ray.
+ *
+ * depth: HOST array of n_frames device pointers to f32[h·w]; dirs_cam
+ * f32[h·w,3] shared by the frames; poses34 device f32[n_frames,12]; packed:
+ * the psvo_pack_tree records of the tree, or NULL (the walk then reads
+ * centres / structure); bits device u32[n_frames, words], zeroed by the call;
+ * flags: one device word, or NULL — bit 0 (the PSVO_STAT_FLAGS DFS-overflow
+ * bit) is OR-ed in when the tree is deeper than the walk's 16-level stack
+ * (such subtrees are not descended).  Asynchronous, no host read-back; one
+ * launch per 64 frames.  PSVO_E_INVALID before any device call: a null
+ * pointer or image, px_step <= 0, h or w <= 0, h·w > 2^24, n_nodes <= 0,
+ * voxel_size <= 0. */
+int64_t psvo_visibility_words(int64_t n_nodes);  /* host only: ceil(n_nodes / 32), 0 for n_nodes <= 0 */
+int psvo_frames_visible(void *stream, int n_frames, int h, int w, int px_step, const float *const *depth,
+                        const float *dirs_cam, const float *poses34, int64_t n_nodes, const void *packed,
+                        const float *centres, const int *structure, float voxel_size, float truncation,
+                        float max_distance, uint32_t *bits, int *flags);
+/* sets u32[n_sets, words], query u32[words] → out i32[n_sets + 1, 2]: row k =
+ * {|S_k ∩ Q|, |S_k|}, the last row {|Q|, |Q|}.  One workgroup per row, no
+ * atomics; asynchronous. */
+int psvo_visibility_overlap(void *stream, int n_sets, int64_t words, const uint32_t *sets, const uint32_t *query,
+                            int *out);
+
 /* ---- tracker <-> mapper state exchange (csrc/share.cpp) ----------------
  * A POSIX shared-memory block `name` ("/…") holds a robust process-shared
  * mutex, PSVO_SHARE_FLAGS int flags (stop_mapping / stop_tracking), the

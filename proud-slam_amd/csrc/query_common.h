@@ -29,6 +29,67 @@ __device__ __forceinline__ int wave_sum(int v) {
     return v;
 }
 
+// ---------------------------------------------------------------------------
+// The slab test and the level bound of every octree walk (query_trace.hip's
+// traversals, covis.hip's visibility walk): one copy, so all of them compare
+// the same values.  Contraction is off inside the bodies whatever the
+// including unit sets (hit indices reproduce the CPU oracle bit for bit).
+constexpr int kLevels = 16;  // octree depth <= 15 (grid_dim <= 32768)
+
+__device__ __forceinline__ bool ray_aabb(const float o[3], const float inv[3], float cx, float cy, float cz,
+                                         float half, float &t_lo, float &t_hi) {
+#pragma clang fp contract(off)
+    float lo_all = 0.0f, hi_all = 100000.0f;
+    const float c[3] = {cx, cy, cz};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float lo = (c[a] - half - o[a]) * inv[a];
+        float hi = (c[a] + half - o[a]) * inv[a];
+        if (hi < lo) {
+            const float tmp = lo;
+            lo = hi;
+            hi = tmp;
+        }
+        if (hi < lo_all) return false;
+        if (lo > hi_all) return false;
+        lo_all = (lo > lo_all) ? lo : lo_all;
+        hi_all = (hi < hi_all) ? hi : hi_all;
+        if (lo_all > hi_all) return false;
+    }
+    t_lo = lo_all;
+    t_hi = hi_all;
+    return true;
+}
+
+// ray_aabb without the early exits: the same comparisons on the same values
+// in the same order (NaNs included), the verdict accumulated instead of
+// returned.  The traversal's node record is then consumed in one basic block,
+// so the compiler cannot sink the y / z loads behind the x test (a second
+// dependent memory round trip per round); t_lo / t_hi are set only on a hit.
+__device__ __forceinline__ bool ray_aabb_nb(const float o[3], const float inv[3], float cx, float cy, float cz,
+                                            float half, float &t_lo, float &t_hi) {
+#pragma clang fp contract(off)
+    float lo_all = 0.0f, hi_all = 100000.0f;
+    bool miss = false;
+    const float c[3] = {cx, cy, cz};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        float lo = (c[a] - half - o[a]) * inv[a];
+        float hi = (c[a] + half - o[a]) * inv[a];
+        const bool sw = hi < lo;
+        const float l2 = sw ? hi : lo, h2 = sw ? lo : hi;
+        miss = miss | (h2 < lo_all) | (l2 > hi_all);
+        lo_all = (l2 > lo_all) ? l2 : lo_all;
+        hi_all = (h2 < hi_all) ? h2 : hi_all;
+        miss = miss | (lo_all > hi_all);
+    }
+    if (!miss) {
+        t_lo = lo_all;
+        t_hi = hi_all;
+    }
+    return !miss;
+}
+
 // Diagnostic build only (-DPSVO_IS_STAMPS, `make is_stamps`: lib/diag/): per
 // ray, k_intersect_sorted's cycles by segment (s_memtime; scalar reads of the
 // clock only), read through psvo_debug_is_stamps (scripts/intersect_stamps.py).

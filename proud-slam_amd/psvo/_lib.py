@@ -146,6 +146,10 @@ _SIGNATURES = {
     "psvo_depth_voxel_keys": (_i32, [_vp, _i64, _vp, _vp, _vp, _f32, _vp, _vp]),
     "psvo_dtree_frame_workspace_bytes": (_i64, [_i32, _i32]),
     "psvo_dtree_insert_depth": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _f32, _vp]),
+    "psvo_visibility_words": (_i64, [_i64]),
+    "psvo_frames_visible": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _f32, _f32, _f32,
+                                   _vp, _vp]),
+    "psvo_visibility_overlap": (_i32, [_vp, _i32, _i64, _vp, _vp, _vp]),
     "psvo_share_block_bytes": (_i64, []),
     "psvo_share_create": (_vp, [ctypes.c_char_p]),
     "psvo_share_attach": (_vp, [ctypes.c_char_p]),
