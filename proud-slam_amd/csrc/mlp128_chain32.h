@@ -118,28 +118,64 @@ __device__ __forceinline__ void init_bias(f32x16 (&acc)[kNB], const float *b, in
         for (int r = 0; r < 16; ++r) acc[ob][r] = b[32 * ob + phi(r, h)];
 }
 
-// ReLU in place; returns the (value > 0) mask, bit 16b + r.  No compares:
-// y = max(v, 0), and t = (−u) & ~u (u = bits of y) has its sign bit set
-// exactly for positive non-zero patterns (±0 clear), so no per-element
-// compare results pile up in SGPR pairs (the compare form spilled ~300 SGPRs).
+// max(v, 0) in one instruction.  fmaxf() on an accumulator element costs two:
+// the compiler does not know an MFMA result to be canonical and quiets it
+// first (v_max v, v, v).  v_med3_f32(v, 0, +inf) needs no such step and gives
+// fmaxf's bits for every input the chain can produce: MAX(v, 0) by the same
+// comparator when nothing is a NaN (−0 → +0, denormals kept), MIN3 = 0 for a
+// quiet NaN.  `inf` is opaque_inf(): with the literal the compiler folds the
+// median back into canonicalise + max.
+__device__ __forceinline__ float opaque_inf() {
+    float inf = __builtin_inff();
+    asm("" : "+s"(inf));
+    return inf;
+}
+__device__ __forceinline__ float relu1(float v, float inf) { return __builtin_amdgcn_fmed3f(v, 0.0f, inf); }
+
+// One element's ReLU mask bit, shifted into `acc` from below: a signed integer
+// compare of y = max(v, 0) against 0 (true exactly for the positive non-zero
+// patterns, denormals included; ±0 false) into VCC, then acc = 2·acc + carry.
+// Both in one statement, so no compare result stays live in an SGPR pair (the
+// compare form written in C++ spilled ~300 SGPRs), and the statement pins the
+// element in program order: the scheduler would otherwise hoist all 64 element
+// computations and keep them live at once.  y is the compiler's own v_max
+// result, a VALU write: no MFMA read hazard inside the statement.  The k-th
+// element shifted in ends at bit 31 − k after 32 of them: mask_word() turns
+// the word round.
+__device__ __forceinline__ void mask_shift_in(uint32_t &acc, float &y) {
+    asm volatile("v_cmp_lt_i32 vcc, 0, %1\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(acc), "+v"(y) : : "vcc");
+}
+__device__ __forceinline__ uint32_t mask_word(uint32_t acc) { return __builtin_bitreverse32(acc); }
+
+// ReLU in place; returns the (value > 0) mask, bit 16b + r: per element the
+// max and mask_shift_in's two instructions.
 __device__ __forceinline__ uint64_t relu(f32x16 (&v)[kNB]) {
     uint32_t half[2] = {0u, 0u};
+    const float inf = opaque_inf();
 #pragma unroll
     for (int b = 0; b < kNB; ++b)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            // pinned in program order: the scheduler would otherwise hoist all
-            // 64 element computations and keep them live at once
-            float y = v[b][r];
-            asm volatile("" : "+v"(y));
-            y = fmaxf(y, 0.0f);
+            float y = relu1(v[b][r], inf);
+            mask_shift_in(half[b >> 1], y);  // element 16 (b & 1) + r of its word, in this order
             v[b][r] = y;
-            const uint32_t u = __float_as_uint(y);
-            const uint32_t t = (0u - u) & ~u;
-            half[b >> 1] |= (t >> 31) << (16 * (b & 1) + r);
-            asm volatile("" : "+v"(half[b >> 1]));
         }
-    return (uint64_t)half[0] | ((uint64_t)half[1] << 32);
+    return (uint64_t)mask_word(half[0]) | ((uint64_t)mask_word(half[1]) << 32);
+}
+
+// ReLU in place, values only (k_mlp_sdf2, the inference forwards: nobody reads
+// a mask): relu()'s values, bit for bit, one max per element.  Pinned in
+// program order like relu()'s elements.
+__device__ __forceinline__ void relu_values(f32x16 (&v)[kNB]) {
+    const float inf = opaque_inf();
+#pragma unroll
+    for (int b = 0; b < kNB; ++b)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float y = relu1(v[b][r], inf);
+            asm volatile("" : "+v"(y));
+            v[b][r] = y;
+        }
 }
 
 // Σ_k w[k] · v[k][sample] over this lane's 64 features (other half via partner lane)
@@ -219,26 +255,27 @@ struct L4Queue {
     }
 };
 
-// relu() restricted to block OB (same per-element sequence and mask bits)
-template <int OB>
+// relu() restricted to block OB (same per-element sequence): `half` collects
+// the blocks' bits as relu()'s words do, blocks in order 0..3, and is turned
+// round by mask_word() after the last one.  MASK false: relu_values()'s.
+template <int OB, bool MASK>
 __device__ __forceinline__ void relu_block(f32x16 &v, uint32_t (&half)[2]) {
+    const float inf = opaque_inf();
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        float y = v[r];
-        asm volatile("" : "+v"(y));
-        y = fmaxf(y, 0.0f);
+        float y = relu1(v[r], inf);
+        if constexpr (MASK)
+            mask_shift_in(half[OB >> 1], y);
+        else
+            asm volatile("" : "+v"(y));
         v[r] = y;
-        const uint32_t u = __float_as_uint(y);
-        const uint32_t t = (0u - u) & ~u;
-        half[OB >> 1] |= (t >> 31) << (16 * (OB & 1) + r);
-        asm volatile("" : "+v"(half[OB >> 1]));
     }
 }
 
 // bacc[OB] += W4 block OB · [f; x] (bias already in bacc), then its ReLU and
 // mask bits (the rgb head's dots wait for all four blocks: until then f is
 // live as the layer input and the registers are spoken for)
-template <int OB>
+template <int OB, bool MASK>
 __device__ __forceinline__ void l4_block(const float *wl, const f32x16 (&a)[kNB], const float (&x)[8],
                                          f32x16 (&bacc)[kNB], int lane, const L4Queue<OB> &q,
                                          uint32_t (&half)[2]) {
@@ -253,7 +290,7 @@ __device__ __forceinline__ void l4_block(const float *wl, const f32x16 (&a)[kNB]
         acc[0] = mfma(w4.z, x[4 * tg + 2], acc[0]);
         acc[0] = mfma(w4.w, x[4 * tg + 3], acc[0]);
     }
-    relu_block<OB>(bacc[OB], half);
+    relu_block<OB, MASK>(bacc[OB], half);
 }
 
 // LDS of the persistent forward kernels: the vectors and W1 resident, then

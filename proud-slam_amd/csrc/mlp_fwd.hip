@@ -105,7 +105,8 @@ __global__ __launch_bounds__(256) void k_mlp_prep(MlpParams p, float *__restrict
 // opens the next layer and drain behind its MFMAs.  LDS: 5 + 8 + 2 × 72 KB.
 //
 // IP (the frame renderer, csrc/render.hip): x is interpolated on chip from
-// `ip` (interp_load.h) instead of read from feat
+// `ip` (interp_load.h) instead of read from feat; inference only — no masks
+// are stored, so none are formed (relu_values: the same activations)
 template <bool H2, bool IP = false>
 __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_fwd2(int64_t m, const float *__restrict__ feat,
                                                             const float *__restrict__ img,
@@ -125,7 +126,8 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_fwd2(int64_t m, const flo
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int h = lane >> 5;
     const bool save = act != nullptr;         // CF activations (weight gradients)
-    const bool save_mask = masks != nullptr;  // ReLU masks (δ chain)
+    constexpr bool kMask = !IP;               // the ReLUs form their masks
+    const bool save_mask = kMask && masks != nullptr;  // ReLU masks (δ chain)
     const int64_t n_tiles = (m + kCh - 1) / kCh * 2;  // CF 32-sample tiles
     const int64_t tstride = n_tiles * 32 * 128;
     const int64_t tbytes = tstride * 4;
@@ -178,7 +180,8 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_fwd2(int64_t m, const flo
         if (active) {
             init_bias(a, lds + kOffB1, h);
             gemm_x(lds + kF2W1, x, a, lane);
-            m1 = relu(a);
+            if constexpr (kMask) m1 = relu(a);
+            else relu_values(a);
         }
         if (h2_given) {  // h1's stores; h2's mask
             if (active) {
@@ -193,7 +196,8 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_fwd2(int64_t m, const flo
             if (active) {
                 init_bias(bacc, lds + kOffB2, h);
                 gemm_acc<kNB, kNB>(buf(seq), a, bacc, lane, CfQueue(cfs, act, tbytes, save, a));  // + h1 stores
-                m2 = relu(bacc);
+                if constexpr (kMask) m2 = relu(bacc);
+                else relu_values(bacc);
             }
             ++seq;
         }
@@ -231,10 +235,10 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_fwd2(int64_t m, const flo
         {
             const float *wl4 = buf(seq);
             const float *fm = act + 2 * tstride, *cm = act + 3 * tstride;
-            l4_block<0>(wl4, a, x, bacc, lane, L4Queue<0>(cfs, fm, cm, tbytes, save, a, bacc), half4);
-            l4_block<1>(wl4, a, x, bacc, lane, L4Queue<1>(cfs, fm, cm, tbytes, save, a, bacc), half4);
-            l4_block<2>(wl4, a, x, bacc, lane, L4Queue<2>(cfs, fm, cm, tbytes, save, a, bacc), half4);
-            l4_block<3>(wl4, a, x, bacc, lane, L4Queue<3>(cfs, fm, cm, tbytes, save, a, bacc), half4);
+            l4_block<0, kMask>(wl4, a, x, bacc, lane, L4Queue<0>(cfs, fm, cm, tbytes, save, a, bacc), half4);
+            l4_block<1, kMask>(wl4, a, x, bacc, lane, L4Queue<1>(cfs, fm, cm, tbytes, save, a, bacc), half4);
+            l4_block<2, kMask>(wl4, a, x, bacc, lane, L4Queue<2>(cfs, fm, cm, tbytes, save, a, bacc), half4);
+            l4_block<3, kMask>(wl4, a, x, bacc, lane, L4Queue<3>(cfs, fm, cm, tbytes, save, a, bacc), half4);
             if (save && cfs.ok) {  // c1 block 3
                 const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
                     const_cast<float *>(cm), 0, __builtin_amdgcn_readfirstlane((int)tbytes), 0x00020000);
@@ -246,7 +250,7 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_fwd2(int64_t m, const flo
             }
         }
         ++seq;
-        const uint64_t m4 = (uint64_t)half4[0] | ((uint64_t)half4[1] << 32);
+        const uint64_t m4 = (uint64_t)mask_word(half4[0]) | ((uint64_t)mask_word(half4[1]) << 32);
         if (save_mask && valid) {
             uint64_t *mk = masks + (s * 2 + h) * 3;
             mk[0] = m1;
@@ -329,10 +333,10 @@ __global__ __launch_bounds__(kF2Threads, 1) void k_mlp_sdf2(int64_t m_host,
         f32x16 a[kNB], bacc[kNB];
         init_bias(a, lds + kOffB1, h);
         gemm_x(lds + kF2W1, x, a, lane);
-        (void)relu(a);
+        relu_values(a);  // no masks: nothing reads them
         init_bias(bacc, lds + kOffB2, h);
         gemm_acc<kNB, kNB>(w2, a, bacc, lane);
-        (void)relu(bacc);
+        relu_values(bacc);
         const float sdf = __fadd_rn(lds[kOffB3], row_dot(lds + kOffW3r0, bacc, h));
         if (valid && h == 0) sdf_out[s] = sdf;
         if (h2_out) store_rows(h2_out, s, valid, kW, bacc, h);  // (the sparse decoder's later layers read it)

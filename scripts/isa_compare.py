@@ -1,15 +1,17 @@
 """Compare the gfx950 device code of two builds, function by function.
 
-    python scripts/isa_compare.py --parent A.s [B.s ...] --new C.s [D.s ...]
+    python scripts/isa_compare.py [--summary] --parent A.s [B.s ...] --new C.s [D.s ...]
 
 The inputs are hipcc's assembly listings (the Makefile's HIPFLAGS plus
 --cuda-device-only -S).  Per function (kernels, and device functions that were
 not inlined) it prints the metadata's VGPR / SGPR / AGPR counts, scratch,
-static LDS and kernarg bytes, the number of instruction / label / directive
-lines and their SHA-1 after normalising (comments stripped; block,
+static LDS and kernarg bytes, the SGPR / VGPR spill counts, the number of MFMA,
+VALU (v_* other than v_mfma*) and s_nop instructions, the number of
+instruction / label / directive lines and their SHA-1 after normalising (comments stripped; block,
 function-end and jump-table labels numbered relative to the function), then a
 unified diff of every function whose stream, .amdhsa_kernel descriptor or
-metadata differ.  It hashes and compares; it runs nothing.
+metadata differ (--summary: the table only).  It hashes and compares; it runs
+nothing.
 """
 import argparse
 import difflib
@@ -20,7 +22,7 @@ import subprocess
 LABEL = re.compile(r"\.L(BB|JTI|func_begin|func_end|tmp)\d+(_?)")
 META = (("vgpr", ".vgpr_count"), ("sgpr", ".sgpr_count"), ("agpr", ".agpr_count"),
         ("scratch", ".private_segment_fixed_size"), ("lds", ".group_segment_fixed_size"),
-        ("kernarg", ".kernarg_segment_size"))
+        ("kernarg", ".kernarg_segment_size"), ("sspill", ".sgpr_spill_count"), ("vspill", ".vgpr_spill_count"))
 
 
 def norm(line):
@@ -86,13 +88,18 @@ def demangle(names):
 def describe(f):
     meta = " ".join(f"{k} {f['meta'].get(key, '?')}" for k, key in META)
     sha = hashlib.sha1("\n".join(f["body"]).encode()).hexdigest()[:12]
-    return f"{meta}  insn-lines {len(f['body'])} sha1 {sha}"
+    ops = [ln.split()[0] for ln in f["body"] if ln.strip()]
+    mfma = sum(o.startswith("v_mfma") for o in ops)
+    valu = sum(o.startswith("v_") for o in ops) - mfma
+    nops = sum(o == "s_nop" for o in ops)
+    return f"{meta}  mfma {mfma} valu {valu} s_nop {nops}  insn-lines {len(f['body'])} sha1 {sha}"
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--parent", nargs="+", required=True)
     ap.add_argument("--new", nargs="+", required=True)
+    ap.add_argument("--summary", action="store_true", help="the per-function table only, no diffs")
     a = ap.parse_args()
     P, N = parse(a.parent), parse(a.new)
     names = sorted(set(P) | set(N))
@@ -118,7 +125,7 @@ def main():
     print()
     print(f"{len(P)} parent functions, {len(N)} new, {len(diffs)} differing, "
           f"{sum(1 for n in names if n not in P or n not in N)} unmatched")
-    for name, d in diffs:
+    for name, d in ([] if a.summary else diffs):
         print(f"\n{name}:")
         for ln in d[2:]:
             print("  " + ln)
